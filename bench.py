@@ -20,6 +20,12 @@ all_reduce(MAX) over the dense actor-indexed state (shard.exchange_vclock).
 `--gpus N` without a launcher starts N rank processes itself (the parent never touches the GPU);
 under torch.distributed.run WORLD_SIZE must equal --gpus.  Prints ONE JSON line (rank 0) and
 exits non-zero if any size-independent result check fails.
+
+A plain run seals the variant-A batch, warms up, times --steps steps, checks the state against
+its closed form and prints the headline line.  `--full` adds everything else to that line: the
+per-kernel times and the roofline block, the shader-clock probe, the host-buffer run, the CPU
+baselines, variant B, the strong-scaling leg (N > 1) and the other BASELINE configs.
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs).
 """
 import argparse
 import ctypes
@@ -387,7 +393,9 @@ class Workload:
             self.out["name"] = fu.result()
         self.names = []
 
-    def run(self, ctx, steps, warmup):
+    def run(self, ctx, steps, warmup, all_kernels=True):
+        """Warm up, time `steps` steps, check the state.  all_kernels: two more (untimed) steps
+        with HIP events around every kernel, for the per-kernel figures (--full)."""
         for _ in range(warmup):
             self.step()
         self.drain_names()
@@ -416,7 +424,10 @@ class Workload:
         if self.world > 1:
             shard.all_reduce_(ms_t, dist.ReduceOp.MAX)
         kern = {k: ctx.timing(k) for k in names}
-        if not time_all:
+        # what the last timed step handed its caller (rank 0), before any later step reuses the
+        # pinned buffer it was downloaded into
+        self.last_file = bytes(self.out["file"]) if self.rank == 0 else None
+        if all_kernels and not time_all:
             ctx.timing_reset()
             ctx.set_timing_only(None)
             ctx.set_timing(True)
@@ -603,11 +614,35 @@ def kernel_summary(w, ms, kern):
             "kernels_ms_per_step": {k: round(v[0] / max(v[1], 1), 4) for k, v in kern.items() if v[1]}}
 
 
+def dump_outputs(d, ctx, w):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files (one
+    value per byte).  The step returns the compacted state file, APP_VERSION(16) || sealed
+    StateWrapper; it is sealed under a fresh random nonce, so two runs agree on the opened
+    plaintext, not on the ciphertext:
+      state.npy      the StateWrapper bytes the file opens to (the product's own AEAD open)
+      file_meta.npy  [file length, the 16 data-version bytes]"""
+    f = w.last_file
+    st, plain = ctx.decrypt(w.key, f[16:])
+    if st:
+        raise SystemExit("bench.py: the last step's state file does not open (status %d)" % st)
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "state.npy"), np.frombuffer(plain, dtype=np.uint8).astype(np.float32))
+    np.save(os.path.join(d, "file_meta.npy"),
+            np.array([len(f)] + list(f[:16]), dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline line: per-kernel and roofline figures, the shader-clock "
+                         "probe, the host-buffer run, the CPU baselines, variant B, the strong-scaling "
+                         "leg (N > 1) and the other BASELINE configs (the --no-* / --configs options "
+                         "below choose among them)")
     ap.add_argument("--versions", type=int, default=256, help="versions per actor per GPU")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="files in the CPU baseline sample (0 = the whole per-GPU workload)")
@@ -626,6 +661,9 @@ def main():
                     help="N > 1: op files by address hash with the cross-rank gate (default), or "
                          "whole writers per rank")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = args.full
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -662,15 +700,18 @@ def main():
     actors_all = actors_table()
 
     wa = Workload(ctx, "a", args, world, rank, dev, actors_all)
-    ms, kern, ok = wa.run(ctx, args.steps, args.warmup)
+    ms, kern, ok = wa.run(ctx, args.steps, args.warmup, all_kernels=full)
     sa = kernel_summary(wa, ms, kern)
-    clock = wa.clock_probe(ctx) if world == 1 and not args.no_clock else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, wa)
+    # everything from here to the result line is behind --full: a plain run times the C2 steps only
+    clock = wa.clock_probe(ctx) if full and world == 1 and not args.no_clock else None
     cpu, cpu_ok = None, True
     hostbuf = None
-    if world == 1 and not args.no_host_buffers:
+    if full and world == 1 and not args.no_host_buffers:
         hostbuf, hb_ok = wa.host_buffer_run(ctx)
         ok = ok and hb_ok
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if full and rank == 0 and world == 1 and not args.no_cpu:
         cpu, cpu_ok = wa.cpu_baseline(args)
     paths_a = sorted(wa.paths)
     wa_total = wa.total_files
@@ -678,7 +719,7 @@ def main():
     del wa
 
     vb = None
-    if not args.no_variant_b:
+    if full and not args.no_variant_b:
         wb = Workload(ctx, "b", args, world, rank, dev, actors_all)
         ms_b, kern_b, ok_b = wb.run(ctx, args.steps, args.warmup)
         ok = ok and ok_b
@@ -692,7 +733,7 @@ def main():
 
     # N > 1: the same 1M-file C2 job split over the N ranks (strong scaling), beside the weak line
     strong = None
-    if world > 1 and not args.no_strong:
+    if full and world > 1 and not args.no_strong:
         ws = Workload(ctx, "a", args, world, rank, dev, actors_all, scaling="strong")
         ms_s, kern_s, ok_s = ws.run(ctx, args.steps, args.warmup)
         ok = ok and ok_s
@@ -711,7 +752,7 @@ def main():
     # and checked by bench_configs.py's runner -- reported beside the C2 line, never its value.
     # N = 1: on this GPU; N > 1: strong scaling over the ranks (bench_configs.run_config)
     configs = None
-    if args.configs:
+    if full and args.configs:
         import bench_configs
         configs = {}
         for c in [x for x in args.configs.split(",") if x]:
@@ -737,38 +778,6 @@ def main():
             torch.cuda.empty_cache()
 
     if rank == 0:
-        fused = os.environ.get("CE_FUSED", str(DEFAULT_FUSED))
-        lpf = 64 // int(os.environ.get("CE_FILES_PER_WAVE", "4"))
-        v3 = fused == "2" and lpf == 16 and not os.environ.get("CE_FUSED_V2")
-        v3b = int(os.environ.get("CE_V3", "2"))
-        kname = ("k_open_fold_v3<%s, %s> (XChaCha20-Poly1305 open + Vec<Dot> decode + fold, lane-owned "
-                 "ChaCha20 blocks, Poly1305 as four-product column sums)"
-                 % ("true" if v3b & 1 else "false", "true" if v3b & 2 else "false") if v3 else
-                 "k_open_fold_v2<%d> (XChaCha20-Poly1305 open + Vec<Dot> decode + fold, "
-                 "lane-owned ChaCha20 blocks)" % lpf if fused == "2" and lpf != 64 else
-                 "k_open_fold_small<%d> (XChaCha20-Poly1305 open + Vec<Dot> decode + fold)" % lpf)
-        kshort = kname.split(" (")[0]
-        traffic = None
-        tf = os.path.join(REPO, "profiles", "traffic_open_fold_small.json")
-        if os.path.exists(tf):
-            with open(tf) as f:
-                rec = json.load(f)
-            # only a measurement of the kernel this run used (and of the same 1M-file launch)
-            if kname.split(" (")[0].rstrip(">") in rec.get("kernel", "") and \
-                    rec.get("files_per_launch") == wa_n(args, world):
-                traffic = rec.get("bytes_per_launch")
-        valu_pmc = None
-        vf = os.path.join(REPO, "profiles", "valu_pmc.json")
-        if os.path.exists(vf) and sa["avg_launch_ms"] > 0:
-            with open(vf) as f:
-                rec = json.load(f).get("fused", {})
-            ipf = rec.get("valu_instr_per_file_per_lane")
-            if ipf and rec.get("kernel", "").replace("void ", "").replace("ce::", "") == kshort:
-                t = wa_n(args, world) * ipf / (sa["avg_launch_ms"] / 1e3) / 1e12
-                valu_pmc = {"instr_per_file": ipf, "achieved_tops": round(t, 2),
-                            "frac_of_peak": round(t / VALU_PEAK_TOPS, 4),
-                            "source": "profiles/valu_pmc.json (rocprofv3 SQ_INSTS_VALU x 64 per "
-                                      "file, same kernel and workload)"}
         line = {
             "metric": METRIC,
             "value": sa["value"],
@@ -800,43 +809,18 @@ def main():
                                if world > 1 else "single GPU",
             },
             "aead_open_GBps": sa["aead_open_GBps"],
-            "roofline": {
-                "kernel": kname,
-                "bound": "valu",
-                "achieved": sa["valu_tops"], "peak": round(VALU_PEAK_TOPS, 1),
-                "unit": "T int32 lane-ops/s", "frac": sa["valu_frac"],
-                "ops_per_file": sa["ops_per_file"], "avg_launch_ms": sa["avg_launch_ms"],
-                "setup_avg_ms": sa["setup_avg_ms"],
-                "traffic": traffic,
-                "ops_formula": "992*ceil(ct/64) + 992 + 960 + 48*(ceil(ct/16)+1) per file (SURVEY.md §8d) "
-                               "x files per launch / (avg fused launch + avg k_open_setup launch), both "
-                               "HIP events on the kernels' stream; the setup runs the HChaCha20 (960) and "
-                               "Poly1305-key block (992) ops",
-                "fused_only": {"ops_per_file": sa["ops_per_file_fused"], "achieved": sa["valu_tops_fused_only"],
-                               "frac": sa["valu_frac_fused_only"],
-                               "note": "the fused kernel alone: §8d less the setup's 1,952 ops per file"},
-                "rocprof": rocprof_frac(sa, wa_n(args, world), kshort),
-                "measured_chacha20_ceiling": {
-                    "tops": round(VALU_CHACHA_TOPS, 1), "keystream_TBps": CHACHA_KS_TBPS,
-                    "frac": round(sa["valu_tops"] / VALU_CHACHA_TOPS, 4),
-                    "source": "profiles/r02_ubench_chacha.txt, profiles/r02_ubench_valu.txt"},
-                "hbm": {"achieved": sa["hbm_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round((sa["hbm_GBps"] or 0) / HBM_PEAK_GBS, 4),
-                        "bytes_per_launch": sa["bytes_per_launch"]},
-                "pmc_valu": valu_pmc,
-                # the peak scales with the shader clock: frac against the peak at the clock the
-                # probe saw beside the fused kernel (VALU_PEAK_TOPS is quoted at 2.4 GHz)
-                "clock": dict(clock, frac_at_measured_clock=round(
-                    sa["valu_frac"] * 2.4 / clock["under_step"]["median_ghz"], 4)) if clock else None,
-            },
-            "kernels_ms_per_step": sa["kernels_ms_per_step"],
             "state_check": "closed-form StateWrapper bytes: %s" % ("ok" if ok else "MISMATCH"),
-            "variant_b": vb,
-            "strong": strong,
-            "host_buffers": hostbuf,
-            "cpu_baseline": cpu,
-            "configs": configs,
         }
+        if full:
+            line.update({
+                "roofline": roofline_report(args, world, sa, clock),
+                "kernels_ms_per_step": sa["kernels_ms_per_step"],
+                "variant_b": vb,
+                "strong": strong,
+                "host_buffers": hostbuf,
+                "cpu_baseline": cpu,
+                "configs": configs,
+            })
         if not (ok and cpu_ok):
             line.pop("value")
             line["error"] = "result check failed: see state_check / cpu_baseline"
@@ -849,6 +833,72 @@ def main():
     ctx.close()
     if int(all_ok.item()) != 1:
         sys.exit(3)
+
+
+def roofline_report(args, world, sa, clock):
+    """--full: the fused kernel's roofline block, from this run's HIP-event times beside the
+    committed profiles of the same kernel and launch size"""
+    fused = os.environ.get("CE_FUSED", str(DEFAULT_FUSED))
+    lpf = 64 // int(os.environ.get("CE_FILES_PER_WAVE", "4"))
+    v3 = fused == "2" and lpf == 16 and not os.environ.get("CE_FUSED_V2")
+    v3b = int(os.environ.get("CE_V3", "2"))
+    kname = ("k_open_fold_v3<%s, %s> (XChaCha20-Poly1305 open + Vec<Dot> decode + fold, lane-owned "
+             "ChaCha20 blocks, Poly1305 as four-product column sums)"
+             % ("true" if v3b & 1 else "false", "true" if v3b & 2 else "false") if v3 else
+             "k_open_fold_v2<%d> (XChaCha20-Poly1305 open + Vec<Dot> decode + fold, "
+             "lane-owned ChaCha20 blocks)" % lpf if fused == "2" and lpf != 64 else
+             "k_open_fold_small<%d> (XChaCha20-Poly1305 open + Vec<Dot> decode + fold)" % lpf)
+    kshort = kname.split(" (")[0]
+    traffic = None
+    tf = os.path.join(REPO, "profiles", "traffic_open_fold_small.json")
+    if os.path.exists(tf):
+        with open(tf) as f:
+            rec = json.load(f)
+        # only a measurement of the kernel this run used (and of the same 1M-file launch)
+        if kname.split(" (")[0].rstrip(">") in rec.get("kernel", "") and \
+                rec.get("files_per_launch") == wa_n(args, world):
+            traffic = rec.get("bytes_per_launch")
+    valu_pmc = None
+    vf = os.path.join(REPO, "profiles", "valu_pmc.json")
+    if os.path.exists(vf) and sa["avg_launch_ms"] > 0:
+        with open(vf) as f:
+            rec = json.load(f).get("fused", {})
+        ipf = rec.get("valu_instr_per_file_per_lane")
+        if ipf and rec.get("kernel", "").replace("void ", "").replace("ce::", "") == kshort:
+            t = wa_n(args, world) * ipf / (sa["avg_launch_ms"] / 1e3) / 1e12
+            valu_pmc = {"instr_per_file": ipf, "achieved_tops": round(t, 2),
+                        "frac_of_peak": round(t / VALU_PEAK_TOPS, 4),
+                        "source": "profiles/valu_pmc.json (rocprofv3 SQ_INSTS_VALU x 64 per "
+                                  "file, same kernel and workload)"}
+    return {
+        "kernel": kname,
+        "bound": "valu",
+        "achieved": sa["valu_tops"], "peak": round(VALU_PEAK_TOPS, 1),
+        "unit": "T int32 lane-ops/s", "frac": sa["valu_frac"],
+        "ops_per_file": sa["ops_per_file"], "avg_launch_ms": sa["avg_launch_ms"],
+        "setup_avg_ms": sa["setup_avg_ms"],
+        "traffic": traffic,
+        "ops_formula": "992*ceil(ct/64) + 992 + 960 + 48*(ceil(ct/16)+1) per file (SURVEY.md §8d) "
+                       "x files per launch / (avg fused launch + avg k_open_setup launch), both "
+                       "HIP events on the kernels' stream; the setup runs the HChaCha20 (960) and "
+                       "Poly1305-key block (992) ops",
+        "fused_only": {"ops_per_file": sa["ops_per_file_fused"], "achieved": sa["valu_tops_fused_only"],
+                       "frac": sa["valu_frac_fused_only"],
+                       "note": "the fused kernel alone: §8d less the setup's 1,952 ops per file"},
+        "rocprof": rocprof_frac(sa, wa_n(args, world), kshort),
+        "measured_chacha20_ceiling": {
+            "tops": round(VALU_CHACHA_TOPS, 1), "keystream_TBps": CHACHA_KS_TBPS,
+            "frac": round(sa["valu_tops"] / VALU_CHACHA_TOPS, 4),
+            "source": "profiles/r02_ubench_chacha.txt, profiles/r02_ubench_valu.txt"},
+        "hbm": {"achieved": sa["hbm_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round((sa["hbm_GBps"] or 0) / HBM_PEAK_GBS, 4),
+                "bytes_per_launch": sa["bytes_per_launch"]},
+        "pmc_valu": valu_pmc,
+        # the peak scales with the shader clock: frac against the peak at the clock the
+        # probe saw beside the fused kernel (VALU_PEAK_TOPS is quoted at 2.4 GHz)
+        "clock": dict(clock, frac_at_measured_clock=round(
+            sa["valu_frac"] * 2.4 / clock["under_step"]["median_ghz"], 4)) if clock else None,
+    }
 
 
 def rocprof_frac(sa, n, kshort):

@@ -19,7 +19,7 @@
                 key (key_cryptor.rs:59-70): every second-key and tampered file must be rejected
                 (CE_ERR_AUTH), every other file accepted, and nothing folded (lib.rs:497-516).
 
-With N > 1 ranks (bench.py --gpus N) every config runs strong-scaled over the ranks
+With N > 1 ranks (bench.py --full --gpus N) every config runs strong-scaled over the ranks
 (run_config -> run_c*_multi below).
 
 Prints one JSON line per run.  Checks (size-independent): the merged clock equals its closed
@@ -1008,7 +1008,7 @@ def run_c5(args, ctx, dev):
 
 
 # ---------------------------------------------------------------------------------------------
-# N > 1 ranks (one process per GPU, torch.distributed; bench.py --gpus N runs these under its
+# N > 1 ranks (one process per GPU, torch.distributed; bench.py --full --gpus N runs these under its
 # `configs` key).  Strong scaling: the config's whole workload is split across the ranks, and
 # value = the job's files / the max-over-ranks step time.
 # ---------------------------------------------------------------------------------------------

@@ -25,13 +25,13 @@ def _port():
 
 
 def test_bench_two_ranks_share_gpu():
-    """bench.py --gpus 2 as the driver's scaling run would start it (here: gloo, both ranks on
+    """bench.py --gpus 2 --full as the driver's scaling run would start it (here: gloo, both ranks on
     the one GPU): the weak C2 line, the strong C2 leg, and C3 / C3r / C4 / C5 at N = 2 under `configs`,
     each with every check true (small sizes: --quick)."""
     env = dict(os.environ, CE_BENCH_SHARE_GPU="1", CE_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--versions",
-                        "2", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-variant-b", "--quick"],
+                        "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-variant-b", "--quick"],
                        env=env, capture_output=True, timeout=400)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     line = json.loads(p.stdout.decode().strip().splitlines()[-1])

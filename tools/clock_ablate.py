@@ -4,7 +4,7 @@ construction (return codes and the state are ignored); only the kernel time and 
 matter."""
 import os
 import sys
-sys.argv = [sys.argv[0]] + ["--steps", "10", "--warmup", "1", "--no-cpu", "--no-variant-b",
+sys.argv = [sys.argv[0]] + ["--full", "--steps", "10", "--warmup", "1", "--no-cpu", "--no-variant-b",
                             "--no-host-buffers"]
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
