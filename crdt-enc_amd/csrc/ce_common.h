@@ -4,7 +4,8 @@
 //   * the reference's version UUIDs (raw big-endian bytes, as Uuid::from_u128 stores them)
 //   * status codes (reference check order; see include/crdtenc.h)
 //   * a bounds-checked msgpack reader implementing rmp-serde 1.x `from_slice` acceptance for the
-//     boxes on the hot path (VersionBytesRef, EncBox, Vec<Dot>, StateWrapper<VClock|GCounter>),
+//     boxes on the hot path (VersionBytesRef, EncBox, Vec<Dot>, Vec<pncounter::Op>,
+//     StateWrapper<VClock|GCounter>),
 //     compiled for both host and device (CE_HD).
 #pragma once
 #include <stddef.h>
@@ -388,6 +389,62 @@ CE_HD int parse_dot(R& r, uint64_t* actor_off, uint64_t* counter) {
     seen |= 1u << f;
     if (f == 0) { if (!rd_uuid(r, actor_off)) return 0; }
     else if (!rd_u64(r, counter)) return 0;
+  }
+  return seen == 3u ? 1 : 0;
+}
+
+// pncounter::Dir (crdts 7, a unit-variant enum): the str "Pos" / "Neg", or a one-entry map whose
+// key is the variant's name or index and whose value is nil.  *dir = 0 Pos, 1 Neg.
+template <typename R>
+CE_HD bool rd_pn_dir(R& r, uint32_t* dir) {
+  static constexpr const char* kV[2] = {"Pos", "Neg"};
+  if (r.i >= r.n) return false;
+  const uint8_t m = rb(r, r.i);
+  if ((m & 0xe0) == 0xa0 || m == 0xd9 || m == 0xda || m == 0xdb) {  // str only: a bin is no variant name
+    const int v = rd_field<2>(r, kV);
+    if (v < 0 || v > 1) return false;
+    *dir = (uint32_t)v;
+    return true;
+  }
+  uint64_t cnt, at;
+  if (!is_map_marker(m) || !rd_map_hdr(r, &cnt) || cnt != 1) return false;
+  const int v = rd_field<2>(r, kV);
+  if (v < 0 || v > 1) return false;
+  if (!rd_take(r, 1, &at) || rb(r, at) != 0xc0) return false;
+  *dir = (uint32_t)v;
+  return true;
+}
+
+// pncounter::Op<Uuid> { dot: Dot<Uuid>, dir: Dir } (crdts 7, derive(Deserialize)): map {"dot",
+// "dir"} in any order (unknown keys ignored, duplicates rejected, both required) or an array of
+// exactly 2.  Returns as parse_dot: 1 ok, 0 decode error, -1 nesting too deep for the device.
+template <typename R>
+CE_HD int parse_pn_op(R& r, uint64_t* actor_off, uint64_t* counter, uint32_t* dir) {
+  static constexpr const char* kF[2] = {"dot", "dir"};
+  if (r.i >= r.n) return 0;
+  const uint8_t m = rb(r, r.i);
+  uint64_t cnt;
+  const bool arr = is_array_marker(m);  // the fields in order, no keys
+  if (arr) {
+    if (!rd_array_hdr(r, &cnt) || cnt != 2) return 0;
+  } else if (!rd_map_hdr(r, &cnt)) {
+    return 0;
+  }
+  unsigned seen = 0;
+  for (uint64_t k = 0; k < cnt; k++) {
+    int f = arr ? (int)k : rd_field<2>(r, kF);
+    if (f < 0) return 0;
+    if (f == 2) {
+      int s = rd_skip(r);
+      if (s <= 0) return s;
+      continue;
+    }
+    if (seen & (1u << f)) return 0;
+    seen |= 1u << f;
+    if (f == 0) {
+      const int d = parse_dot(r, actor_off, counter);
+      if (d <= 0) return d;
+    } else if (!rd_pn_dir(r, dir)) return 0;
   }
   return seen == 3u ? 1 : 0;
 }

@@ -1,9 +1,10 @@
 // ce_core.cpp -- Core<S, Storage, Cryptor, _> (crdt-enc/src/lib.rs:188-723), driving the GPU
-// batch engine.  S = VClock<Uuid> / GCounter<Uuid> live here; S = Orswot<u64, Uuid> /
+// batch engine.  S = VClock<Uuid> / GCounter<Uuid> / PNCounter<Uuid> live here; S = Orswot<u64, Uuid> /
 // MVReg<u64, Uuid> (the dot-set kinds) dispatch to ce_dotset_host.cpp.
 //
 // State layout: a host-built open-addressing actor table (UUID -> dense slot) mirrored in HBM;
-// the CRDT state (VClock dots / GCounter.inner) is a dense u64[cap] max-register array in HBM;
+// the CRDT state (VClock dots / GCounter.inner) is a dense u64[cap] max-register array in HBM
+// (PNCounter: u64[2 cap], p.inner at [slot] and n.inner at [slot + cap]);
 // next_op_versions (lib.rs:741) is a dense u64[cap] on the host (the version gate runs there
 // while the GPU decrypts).  Serialization sorts slots by UUID bytes = BTreeMap order.
 #include <algorithm>
@@ -153,10 +154,15 @@ bool read_vclock(Rd& r, Dots* out) {
 }
 
 // StateWrapper<S> { next_op_versions: VClock, state: S } (lib.rs:739-743)
-bool read_state_wrapper(const uint8_t* p, size_t n, int kind, Dots* nov, Dots* st) {
+// stn (PNCounter): the n counter's dots; state = { p: GCounter, n: GCounter }
+bool read_state_wrapper(const uint8_t* p, size_t n, int kind, Dots* nov, Dots* st, Dots* stn) {
   Rd r{p, n, 0};
   return read_struct(r, {"next_op_versions", "state"}, [&](int f, Rd& q) {
     if (f == 0) return read_vclock(q, nov);
+    if (kind == CE_STATE_PNCOUNTER)
+      return read_struct(q, {"p", "n"}, [&](int g, Rd& q2) {
+        return read_struct(q2, {"inner"}, [&](int, Rd& q3) { return read_vclock(q3, g == 0 ? st : stn); });
+      });
     if (kind == CE_STATE_GCOUNTER)
       return read_struct(q, {"inner"}, [&](int, Rd& q2) { return read_vclock(q2, st); });
     return read_vclock(q, st);
@@ -196,6 +202,22 @@ bool read_dots(const uint8_t* p, size_t n, Dots* out) {
     std::memcpy(a.data(), q.p + aoff, 16);
     out->push_back({a, c});
     r = q;
+  }
+  return true;
+}
+
+// Vec<pncounter::Op<Uuid>>: pos / neg = the Dots of each direction
+bool read_pn_ops(const uint8_t* p, size_t n, Dots* pos, Dots* neg) {
+  Rd r{p, n, 0};
+  uint64_t cnt;
+  if (!rd_array_hdr(r, &cnt) || cnt > n) return false;
+  for (uint64_t k = 0; k < cnt; k++) {
+    uint64_t aoff = 0, c = 0;
+    uint32_t dir = 0;
+    if (parse_pn_op(r, &aoff, &c, &dir) != 1) return false;  // (too deep for the bounded skip: rejected)
+    Uuid a;
+    std::memcpy(a.data(), r.p + aoff, 16);
+    (dir ? neg : pos)->push_back({a, c});
   }
   return true;
 }
@@ -263,10 +285,11 @@ int table_init(ce_core* c, uint32_t cap) {
   c->slot_of.clear();
   c->table_dirty = true;
   hipError_t e;
-  if ((e = c->d_table.reserve(cap * sizeof(ActorSlot))) || (e = c->d_state.reserve(cap * 8ull)) ||
-      (e = c->d_batch.reserve(cap * 8ull)) || (e = c->d_tmp.reserve(cap * 8ull)))
+  const uint64_t words = (uint64_t)state_planes(c->kind) * cap;
+  if ((e = c->d_table.reserve(cap * sizeof(ActorSlot))) || (e = c->d_state.reserve(words * 8ull)) ||
+      (e = c->d_batch.reserve(words * 8ull)) || (e = c->d_tmp.reserve(words * 8ull)))
     return c->ctx->hip_fail(e, "actor table");
-  if ((e = hipMemsetAsync(c->d_state.p, 0, cap * 8ull, c->ctx->stream)))
+  if ((e = hipMemsetAsync(c->d_state.p, 0, words * 8ull, c->ctx->stream)))
     return c->ctx->hip_fail(e, "actor table");
   return CE_OK;
 }
@@ -285,20 +308,22 @@ int table_upload(ce_core* c) {
 int table_grow(ce_core* c) {
   // rehash into 2x capacity; move the dense state (device) and nov (host) with it
   const uint32_t old_cap = c->cap;
-  std::vector<uint64_t> st(old_cap);
+  const uint32_t planes = state_planes(c->kind);
+  std::vector<uint64_t> st((size_t)planes * old_cap);
   hipError_t e;
-  if ((e = hipMemcpyAsync(st.data(), c->d_state.p, old_cap * 8ull, hipMemcpyDeviceToHost,
+  if ((e = hipMemcpyAsync(st.data(), c->d_state.p, st.size() * 8ull, hipMemcpyDeviceToHost,
                           c->ctx->stream)) ||
       (e = stream_wait(c->ctx->stream)))
     return c->ctx->hip_fail(e, "grow");
   std::vector<Uuid> actors;
-  std::vector<uint64_t> nov, sv;
+  std::vector<uint64_t> nov, sv, sv2;
   std::vector<uint32_t> ids;
   for (uint32_t s = 0; s < old_cap; s++)
     if (c->h_table[s].used) {
       actors.push_back(c->slot_actor[s]);
       nov.push_back(c->nov[s]);
       sv.push_back(st[s]);
+      if (planes == 2) sv2.push_back(st[(size_t)old_cap + s]);
       ids.push_back(c->h_table[s].pad[0]);
     }
   const std::vector<Uuid> id_actor = c->id_actor;
@@ -307,7 +332,7 @@ int table_grow(ce_core* c) {
   DevBuf keep_state;
   int rc = table_init(c, old_cap * 2);
   if (rc) return rc;
-  std::vector<uint64_t> nst(c->cap, 0);
+  std::vector<uint64_t> nst((size_t)planes * c->cap, 0);
   for (size_t i = 0; i < actors.size(); i++) {
     bool found;
     const uint32_t s = probe_slot(c->h_table, c->cap - 1, actors[i], &found);
@@ -318,11 +343,12 @@ int table_grow(ce_core* c) {
     c->slot_of[actors[i]] = s;
     c->nov[s] = nov[i];
     nst[s] = sv[i];
+    if (planes == 2) nst[(size_t)c->cap + s] = sv2[i];
     c->size++;
   }
   c->id_actor = id_actor;
   c->registered = reg;
-  if ((e = hipMemcpyAsync(c->d_state.p, nst.data(), c->cap * 8ull, hipMemcpyHostToDevice,
+  if ((e = hipMemcpyAsync(c->d_state.p, nst.data(), nst.size() * 8ull, hipMemcpyHostToDevice,
                           c->ctx->stream)) ||
       (e = stream_wait(c->ctx->stream)))
     return c->ctx->hip_fail(e, "grow");
@@ -352,9 +378,9 @@ int insert_actor(ce_core* c, const Uuid& u, uint32_t* slot) {
 }
 
 int download_state(ce_core* c, std::vector<uint64_t>* st) {
-  st->resize(c->cap);
+  st->resize((size_t)state_planes(c->kind) * c->cap);
   hipError_t e;
-  if ((e = hipMemcpyAsync(st->data(), c->d_state.p, c->cap * 8ull, hipMemcpyDeviceToHost,
+  if ((e = hipMemcpyAsync(st->data(), c->d_state.p, st->size() * 8ull, hipMemcpyDeviceToHost,
                           c->ctx->stream)) ||
       (e = stream_wait(c->ctx->stream)))
     return c->ctx->hip_fail(e, "state download");
@@ -371,26 +397,35 @@ void refresh_slots(ce_core* c, const uint8_t* actors, uint32_t m, std::vector<ui
   }
 }
 
-int merge_dots_host(ce_core* c, const Dots& dots) {
-  if (dots.empty()) return CE_OK;
-  std::vector<std::pair<uint32_t, uint64_t>> sv;
-  const uint64_t gen0 = c->table_gen;
+int merge_dots_host(ce_core* c, const Dots& dots, const Dots* neg) {
+  const size_t nneg = neg ? neg->size() : 0;
+  if (dots.empty() && nneg == 0) return CE_OK;
+  // every actor gets its slot before any is used: a growth moves the ones handed out before it
   for (auto& d : dots) {
     uint32_t s;
     int rc = insert_actor(c, d.first, &s);
     if (rc) return rc;
-    sv.push_back({s, d.second});
   }
-  // a growth during the loop moved every slot handed out before it
-  if (c->table_gen != gen0)
-    for (size_t i = 0; i < dots.size(); i++) sv[i].first = c->slot_of.at(dots[i].first);
-  std::vector<uint64_t> dense(c->cap, 0);
-  for (auto& p : sv) dense[p.first] = std::max(dense[p.first], p.second);
+  for (size_t i = 0; i < nneg; i++) {
+    uint32_t s;
+    int rc = insert_actor(c, (*neg)[i].first, &s);
+    if (rc) return rc;
+  }
+  const uint32_t words = state_planes(c->kind) * c->cap;
+  std::vector<uint64_t> dense(words, 0);
+  for (auto& d : dots) {
+    uint64_t& x = dense[c->slot_of.at(d.first)];
+    x = std::max(x, d.second);
+  }
+  for (size_t i = 0; i < nneg; i++) {  // the n plane
+    uint64_t& x = dense[c->cap + c->slot_of.at((*neg)[i].first)];
+    x = std::max(x, (*neg)[i].second);
+  }
   hipError_t e;
-  if ((e = hipMemcpyAsync(c->d_tmp.p, dense.data(), c->cap * 8ull, hipMemcpyHostToDevice,
+  if ((e = hipMemcpyAsync(c->d_tmp.p, dense.data(), words * 8ull, hipMemcpyHostToDevice,
                           c->ctx->stream)) ||
       (e = launch_merge_max(c->ctx->stream, c->d_state.as<unsigned long long>(),
-                            c->d_tmp.as<unsigned long long>(), c->cap)) ||
+                            c->d_tmp.as<unsigned long long>(), words)) ||
       (e = stream_wait(c->ctx->stream)))
     return c->ctx->hip_fail(e, "merge dots");
   return CE_OK;
@@ -415,12 +450,15 @@ int serialize_state(ce_core* c, std::vector<uint8_t>* out) {
   if (rc) return rc;
   ensure_sorted(c);
   const std::vector<uint32_t>& slots = c->sorted_slots;
-  size_t n_nov = 0, n_st = 0;
+  const bool pnc = c->kind == CE_STATE_PNCOUNTER;
+  size_t n_nov = 0, n_st = 0, n_neg = 0;
   for (uint32_t s : slots) { n_nov += c->nov[s] != 0; n_st += st[s] != 0; }
+  if (pnc)
+    for (uint32_t s : slots) n_neg += st[(size_t)c->cap + s] != 0;
   Wr w;
   w.b.swap(*out);  // reuse the caller's capacity
   w.b.clear();
-  w.b.reserve(64 + 28 * (n_nov + n_st));
+  w.b.reserve(96 + 28 * (n_nov + n_st + n_neg));
   w.map(2);
   w.str("next_op_versions");
   w.map(1);
@@ -429,12 +467,25 @@ int serialize_state(ce_core* c, std::vector<uint8_t>* out) {
   for (uint32_t s : slots)
     if (c->nov[s]) { w.bin(c->slot_actor[s].data(), 16); w.uint(c->nov[s]); }
   w.str("state");
-  if (c->kind == CE_STATE_GCOUNTER) { w.map(1); w.str("inner"); }
+  if (pnc) { w.map(2); w.str("p"); }  // PNCounter { p: GCounter, n: GCounter }
+  if (c->kind == CE_STATE_GCOUNTER || pnc) { w.map(1); w.str("inner"); }
   w.map(1);
   w.str("dots");
   w.map(n_st);
   for (uint32_t s : slots)
     if (st[s]) { w.bin(c->slot_actor[s].data(), 16); w.uint(st[s]); }
+  if (pnc) {
+    w.str("n");
+    w.map(1);
+    w.str("inner");
+    w.map(1);
+    w.str("dots");
+    w.map(n_neg);
+    for (uint32_t s : slots) {
+      const uint64_t v = st[(size_t)c->cap + s];
+      if (v) { w.bin(c->slot_actor[s].data(), 16); w.uint(v); }
+    }
+  }
   out->swap(w.b);
   return CE_OK;
 }
@@ -566,6 +617,12 @@ using AfterCommit = std::function<int(NovApply&)>;
 // table, so the next pass finds them.
 static constexpr int kRestartIngest = -1000;
 
+// the whole-file decode of the core's op grammar: Vec<Dot>, or Vec<pncounter::Op> into two planes
+static hipError_t launch_decode_ops(ce_core* c, const DecodeArgs& da, uint32_t grid_waves) {
+  return c->kind == CE_STATE_PNCOUNTER ? launch_decode_pn_ops(c->ctx->stream, da, grid_waves)
+                                       : launch_decode_dots(c->ctx->stream, da, grid_waves);
+}
+
 // Decode + fold the files flagged in d_mask (n bytes) whose plaintext sits in ctx->out
 // (k_decode_dots), with actor-table misses resolved as the fused path does (insert, upload,
 // fold the missed files again).  Returns kRestartIngest when the table had to grow.
@@ -582,7 +639,7 @@ int decode_only_resolving(ce_core* c, DecodeArgs& da, uint32_t n, uint8_t* d_mas
     da.batch = c->d_batch.as<unsigned long long>();
     if ((e = hipMemsetAsync(ctx->counters.as<uint32_t>() + 4, 0, 4, ctx->stream)) ||
         (e = hipMemsetAsync(ctx->refold.p, 0, n, ctx->stream)) ||
-        (e = launch_decode_dots(ctx->stream, da, grid_waves_for(n))) ||
+        (e = launch_decode_ops(c, da, grid_waves_for(n))) ||
         (e = hipMemcpyAsync(hc, ctx->counters.p, 64, hipMemcpyDeviceToHost, ctx->stream)) ||
         (e = stream_wait(ctx->stream)))
       return ctx->hip_fail(e, "decode plaintext");
@@ -663,6 +720,9 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
     return ds_ingest_ops(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, status_out);
   hipError_t e;
   const KeyRef key = key_of(c);
+  const bool pnc = c->kind == CE_STATE_PNCOUNTER;
+  // words of the dense state and batch (both planes), at the table's current capacity
+  auto words = [&] { return (uint64_t)state_planes(c->kind) * c->cap; };
   // writer actors (the op directories) get slots first: the version gate is keyed by them
   // (a repeated writer list -- the same shard every step -- reuses the previous lookup)
   std::vector<uint32_t> wslot;
@@ -750,7 +810,7 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
   {
     FillArgs fl{};
     fl.r[0] = {reinterpret_cast<uint32_t*>(gbase + 16ull * m), 4ull * m, 0u};  // newnov, runs
-    fl.r[1] = {c->d_batch.as<uint32_t>(), 2ull * c->cap, 0u};
+    fl.r[1] = {c->d_batch.as<uint32_t>(), 2ull * words(), 0u};
     fl.r[2] = {ctx->refold.as<uint32_t>(), (n + 3ull) / 4, 0u};
     fl.r[3] = {ctx->redo.as<uint32_t>(), (n + 3ull) / 4, 0u};
     fl.n = 4;
@@ -846,7 +906,11 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
   auto run_fold = [&](const uint8_t* only) -> int {
     da.only = only;
     da.large_only = 1;
-    if (c->fused == 2 && c->files_per_wave != 1) {
+    if (pnc) {  // always the default geometry's PNCounter form (no env-selected alternates)
+      hipEvent_t t0, t1;
+      (void)ctx->tlaunch("open_fold_small", &t0, &t1);
+      if ((e = launch_open_fold_pn(ctx->stream, da, t0, t1))) return ctx->hip_fail(e, "fused");
+    } else if (c->fused == 2 && c->files_per_wave != 1) {
       hipEvent_t t0, t1;
       (void)ctx->tlaunch("open_fold_small", &t0, &t1);
       if ((e = launch_open_fold_v2(ctx->stream, da, c->files_per_wave, t0, t1))) return ctx->hip_fail(e, "fused");
@@ -876,8 +940,10 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
     if (n_large == 0) return CE_OK;  // every file was single-page: nothing for the kernels below
     // decode inside the segment pass (CE_SEGDEC=0 or CE_SPLIT=1: the separate decode kernels
     // below; read per call, as CE_SPLIT)
+    // (PNCounter: neither -- both decode the Dot grammar; its multi-page files are opened to HBM
+    // and decoded whole by k_decode_pn_ops)
     const char* sdv = getenv("CE_SEGDEC");
-    const bool segdec = !(sdv && sdv[0] == '0') && !getenv("CE_SPLIT");
+    const bool segdec = !pnc && !(sdv && sdv[0] == '0') && !getenv("CE_SPLIT");
     if (!only) {
       SegScratch sc = segscratch(ctx, ec);
       if (segdec && (e = ctx->segrec.reserve((size_t)ec * 2 * 32))) return ctx->hip_fail(e, "segment records");
@@ -907,10 +973,10 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
     }
     const int t = ctx->tbegin("decode");
     // CE_SPLIT=1: k_decode_split (measured slower on C4: 1.67 vs 1.36 ms)
-    if (only || !getenv("CE_SPLIT")) {
+    if (only || pnc || !getenv("CE_SPLIT")) {
       // counters[15]: the large-file list's pull index (k_decode_dots, large_only && !only),
       // zeroed with the counter block
-      if ((e = launch_decode_dots(ctx->stream, da, grid_waves_for(n))))
+      if ((e = launch_decode_ops(c, da, grid_waves_for(n))))
         return ctx->hip_fail(e, "decode");
     } else {
       // every record a file's apply step reads is written by this batch's parts (no memset)
@@ -928,7 +994,7 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
   if (!sharded && !after_commit) {
     const int t = ctx->tbegin("merge");
     if ((e = launch_merge_max_if(ctx->stream, c->d_state.as<unsigned long long>(),
-                                 c->d_batch.as<unsigned long long>(), c->cap,
+                                 c->d_batch.as<unsigned long long>(), (uint32_t)words(),
                                  ctx->counters.as<uint32_t>())))
       return ctx->hip_fail(e, "merge");
     ctx->tend(t);
@@ -942,7 +1008,7 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
     if (!sharded) {
       na.merge_dst = c->d_state.as<unsigned long long>();
       na.merge_src = c->d_batch.as<unsigned long long>();
-      na.merge_n = c->cap;
+      na.merge_n = (uint32_t)words();
     }
     if ((rc = (*after_commit)(na))) return rc;
     host_tail = na.host_tail;  // it downloads the counters and newnov with its own tail
@@ -1006,7 +1072,7 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
     first_gap = host_gate(fa.data(), fv.data(), n, &expect, ap.data());
     host_gated = true;
     if ((e = hipMemcpyAsync(ctx->apply.p, ap.data(), n, hipMemcpyHostToDevice, ctx->stream)) ||
-        (e = hipMemsetAsync(c->d_batch.p, 0, c->cap * 8ull, ctx->stream)) ||
+        (e = hipMemsetAsync(c->d_batch.p, 0, words() * 8ull, ctx->stream)) ||
         (e = hipMemsetAsync(c->d_refold2.p, 1, n, ctx->stream)) ||
         (e = hipMemsetAsync(ctx->refold.p, 0, n, ctx->stream)) ||
         (e = hipMemsetAsync(ctx->counters.as<uint32_t>() + 4, 0, 4, ctx->stream)))
@@ -1039,7 +1105,7 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
     }
     if (c->cap != old_cap) {
       // slots moved: the partial batch state is stale -> fold everything again
-      if ((e = hipMemsetAsync(c->d_batch.p, 0, c->cap * 8ull, ctx->stream)) ||
+      if ((e = hipMemsetAsync(c->d_batch.p, 0, words() * 8ull, ctx->stream)) ||
           (e = hipMemsetAsync(c->d_refold2.p, 1, n, ctx->stream)))
         return ctx->hip_fail(e, "miss");
     }
@@ -1120,7 +1186,7 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
   } else {
     const int t = ctx->tbegin("merge");
     if ((e = launch_merge_max(ctx->stream, c->d_state.as<unsigned long long>(),
-                              c->d_batch.as<unsigned long long>(), c->cap)))
+                              c->d_batch.as<unsigned long long>(), (uint32_t)words())))
       return ctx->hip_fail(e, "merge");
     ctx->tend(t);
     if (!host_gated) {
@@ -1287,7 +1353,7 @@ int ingest_states_dev(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs,
   }
   // host pass: StateWrapper msgpack -> dots (north star: "host pass that flattens decoded
   // ops/states into columnar arrays")
-  std::vector<Dots> novs(n), sts(n);
+  std::vector<Dots> novs(n), sts(n), negs(n);  // negs: PNCounter's n plane
   int first = CE_OK;
   for (uint32_t i = 0; i < n; i++) {
     if (st[i] == CE_OK) {
@@ -1298,7 +1364,7 @@ int ingest_states_dev(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs,
         Uuid v;
         std::memcpy(v.data(), pt, 16);
         if (!std::binary_search(c->supported.begin(), c->supported.end(), v)) st[i] = CE_ERR_PT_VERSION;
-        else if (!read_state_wrapper(pt + 16, len - 16, c->kind, &novs[i], &sts[i]))
+        else if (!read_state_wrapper(pt + 16, len - 16, c->kind, &novs[i], &sts[i], &negs[i]))
           st[i] = CE_ERR_DECODE;
       }
     }
@@ -1307,9 +1373,12 @@ int ingest_states_dev(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs,
   if (status_out) std::memcpy(status_out, st.data(), n * 4ull);
   if (first != CE_OK) return first;
   // fold (lib.rs:458-466): state.merge(sw.state); next_op_versions.merge(sw.next_op_versions)
-  Dots all;
-  for (uint32_t i = 0; i < n; i++) all.insert(all.end(), sts[i].begin(), sts[i].end());
-  if ((rc = merge_dots_host(c, all))) return rc;
+  Dots all, alln;
+  for (uint32_t i = 0; i < n; i++) {
+    all.insert(all.end(), sts[i].begin(), sts[i].end());
+    alln.insert(alln.end(), negs[i].begin(), negs[i].end());
+  }
+  if ((rc = merge_dots_host(c, all, &alln))) return rc;
   for (uint32_t i = 0; i < n; i++)
     for (auto& d : novs[i]) {
       uint32_t s;
@@ -1407,7 +1476,8 @@ int compact_enqueue(ce_core* c, ce_ctx* x, const uint8_t* nonce, NovApply* na, C
       return x->hip_fail(e, "sorted slots");
     c->d_sorted_gen = c->sorted_gen;
   }
-  const uint64_t U = vclock_ser_bound(k);             // clear length bound (prefix included)
+  const bool pnc = c->kind == CE_STATE_PNCOUNTER;
+  const uint64_t U = vclock_ser_bound(k, pnc);        // clear length bound (prefix included)
   const uint64_t A = (U + 255) & ~255ull;              // small arguments after the clear text
   const uint64_t total_max = 16 + sealed_len(U);
   const uint64_t T = (total_max + 255) & ~255ull;      // the packed tail after the file bound
@@ -1445,7 +1515,7 @@ int compact_enqueue(ce_core* c, ce_ctx* x, const uint8_t* nonce, NovApply* na, C
   auto* d_offs = reinterpret_cast<unsigned long long*>(db + A);
   if ((e = launch_serialize_vclock(x->stream, nov, c->d_state.as<unsigned long long>(), c->d_sorted.as<uint32_t>(),
                                    k, c->d_table.as<ActorSlot>(), c->kind == CE_STATE_GCOUNTER,
-                                   ingest_fmt ? db + A + 64 : nullptr, db, d_offs)))
+                                   ingest_fmt ? db + A + 64 : nullptr, db, d_offs, pnc ? c->cap : 0u)))
     return x->hip_fail(e, "serialize");
   rc = device_seal(x, db, reinterpret_cast<const uint64_t*>(d_offs), 1, U, db + A + 48, db + A + 24,
                    x->out.as<uint8_t>(), reinterpret_cast<const uint64_t*>(db + A + 16), key, true);
@@ -1533,7 +1603,7 @@ int ce_core_open(ce_ctx* ctx, const ce_open_options* o, ce_core** out) {
   if (!ctx || !o || !out || !o->current_data_version || (o->n_supported && !o->supported_data_versions))
     return CE_ERR_INVALID_ARG;
   if (o->state_kind != CE_STATE_VCLOCK && o->state_kind != CE_STATE_GCOUNTER &&
-      !is_dotset_kind(o->state_kind))
+      o->state_kind != CE_STATE_PNCOUNTER && !is_dotset_kind(o->state_kind))
     return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(ctx->mu);
   (void)hipSetDevice(ctx->device);
@@ -1998,11 +2068,13 @@ int ce_core_apply_ops(ce_core* c, const uint8_t* ops, size_t len) {
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
   (void)hipSetDevice(c->ctx->device);
   if (!c->has_key) return c->ctx->fail(CE_ERR_NO_KEY, "no latest key");
-  Dots dots;
+  Dots dots, neg;  // neg: a PNCounter's Neg ops
   const bool ds = is_dotset_kind(c->kind);
   if (ds) {
     int rc = ds_check_ops(c, ops, len);
     if (rc) return rc;
+  } else if (c->kind == CE_STATE_PNCOUNTER) {
+    if (!read_pn_ops(ops, len, &dots, &neg)) return c->ctx->fail(CE_ERR_DECODE, "ops are not a Vec<pncounter::Op<Uuid>>");
   } else if (!read_dots(ops, len, &dots)) {
     return c->ctx->fail(CE_ERR_DECODE, "ops are not a Vec<Dot<Uuid>>");
   }
@@ -2018,7 +2090,7 @@ int ce_core_apply_ops(ce_core* c, const uint8_t* ops, size_t len) {
   if (c->storage && (rc = storage_store_op(c->storage, c->local_actor, version, file.data(), file.size())))
     return c->ctx->fail(rc, "failed writing ops file");
   // state.apply(op) for op in ops (lib.rs:710-712)
-  if ((rc = ds ? ds_apply_local_ops(c, ops, len) : merge_dots_host(c, dots))) return rc;
+  if ((rc = ds ? ds_apply_local_ops(c, ops, len) : merge_dots_host(c, dots, &neg))) return rc;
   // the apply may have grown the table (new Dot actors), which moves every slot: look it up again
   s = c->slot_of.at(c->local_actor);
   c->nov[s] = version + 1;                         // next_op_versions.inc(actor) (lib.rs:714-715)
@@ -2037,13 +2109,16 @@ int ce_core_apply_ops_batch(ce_core* c, const uint8_t* ops, const uint64_t* offs
   ce_ctx* ctx = c->ctx;
   if (!c->has_key) return ctx->fail(CE_ERR_NO_KEY, "no latest key");
   const bool ds = is_dotset_kind(c->kind);
-  std::vector<Dots> dots(ds ? 0 : n);
+  std::vector<Dots> dots(ds ? 0 : n), negs(ds ? 0 : n);
   for (uint32_t i = 0; i < n; i++) {
     const uint8_t* p = ops + offs[i];
     const size_t l = offs[i + 1] - offs[i];
     if (ds) {
       int rc = ds_check_ops(c, p, l);
       if (rc) return rc;
+    } else if (c->kind == CE_STATE_PNCOUNTER) {
+      if (!read_pn_ops(p, l, &dots[i], &negs[i]))
+        return ctx->fail(CE_ERR_DECODE, "ops are not a Vec<pncounter::Op<Uuid>>");
     } else if (!read_dots(p, l, &dots[i])) {
       return ctx->fail(CE_ERR_DECODE, "ops are not a Vec<Dot<Uuid>>");
     }
@@ -2097,7 +2172,8 @@ int ce_core_apply_ops_batch(ce_core* c, const uint8_t* ops, const uint64_t* offs
                                              foffs[i + 1] - foffs[i])))
       return ctx->fail(rc, "failed writing ops file");
     // state.apply(op) for op in ops (lib.rs:710-712), then next_op_versions.inc (lib.rs:714-715)
-    if ((rc = ds ? ds_apply_local_ops(c, ops + offs[i], offs[i + 1] - offs[i]) : merge_dots_host(c, dots[i])))
+    if ((rc = ds ? ds_apply_local_ops(c, ops + offs[i], offs[i + 1] - offs[i])
+                 : merge_dots_host(c, dots[i], &negs[i])))
       return rc;
     s = c->slot_of.at(c->local_actor);  // a growth inside the apply moved the local actor's slot
     c->nov[s] = v0 + i + 1;
@@ -2121,7 +2197,7 @@ int ce_core_reset(ce_core* c) {
   std::fill(c->nov.begin(), c->nov.end(), 0);
   c->read_states.clear();
   if (is_dotset_kind(c->kind)) return ds_reset(c);  // (the dense state array is the VClock kinds')
-  hipError_t e = hipMemsetAsync(c->d_state.p, 0, c->cap * 8ull, c->ctx->stream);
+  hipError_t e = hipMemsetAsync(c->d_state.p, 0, (uint64_t)state_planes(c->kind) * c->cap * 8ull, c->ctx->stream);
   if (e) return c->ctx->hip_fail(e, "reset");
   return CE_OK;
 }
@@ -2164,13 +2240,13 @@ uint64_t ce_core_path_count(ce_core* c, const char* path) {
 }
 
 int ce_core_dense_ready(ce_core* c) {
-  if (!c || is_dotset_kind(c->kind)) return 0;
+  if (!c || no_dense_exchange(c->kind)) return 0;
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
   return c->registered == c->size ? 1 : 0;
 }
 
 int ce_core_export_dense(ce_core* c, uint64_t* d_state, uint64_t* d_nov) {
-  if (!c || !d_state || !d_nov || is_dotset_kind(c->kind)) return CE_ERR_INVALID_ARG;
+  if (!c || !d_state || !d_nov || no_dense_exchange(c->kind)) return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
   if (c->registered != c->size) return c->ctx->fail(CE_ERR_INVALID_ARG, "actors outside the registered set");
   hipError_t e;
@@ -2182,7 +2258,7 @@ int ce_core_export_dense(ce_core* c, uint64_t* d_state, uint64_t* d_nov) {
 }
 
 int ce_core_import_dense(ce_core* c, const uint64_t* d_state, const uint64_t* d_nov) {
-  if (!c || !d_state || !d_nov || is_dotset_kind(c->kind)) return CE_ERR_INVALID_ARG;
+  if (!c || !d_state || !d_nov || no_dense_exchange(c->kind)) return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
   if (c->registered != c->size) return c->ctx->fail(CE_ERR_INVALID_ARG, "actors outside the registered set");
   std::vector<uint64_t> nv(c->cap);
@@ -2205,10 +2281,10 @@ int ce_core_merge_state(ce_core* c, const uint8_t* sw, size_t len) {
     int32_t st = CE_OK;
     return ds_merge_states(c, sws, &st, nullptr);
   }
-  Dots nov, state;
-  if (!read_state_wrapper(sw, len, c->kind, &nov, &state))
+  Dots nov, state, neg;
+  if (!read_state_wrapper(sw, len, c->kind, &nov, &state, &neg))
     return c->ctx->fail(CE_ERR_DECODE, "not a StateWrapper");
-  int rc = merge_dots_host(c, state);  // state.merge(sw.state) (lib.rs:460)
+  int rc = merge_dots_host(c, state, &neg);  // state.merge(sw.state) (lib.rs:460)
   if (rc) return rc;
   for (auto& d : nov) {                // next_op_versions.merge(..) (lib.rs:461-463)
     uint32_t s;

@@ -35,6 +35,12 @@ struct DsState;  // Orswot / MVReg state (ce_dotset_host.cpp)
 void ds_free(DsState* d);
 
 inline bool is_dotset_kind(int kind) { return kind == CE_STATE_ORSWOT || kind == CE_STATE_MVREG; }
+// kinds without the dense multi-GPU exchange (export / import / sharded ingest / pending batch):
+// their ranks exchange state bytes instead
+inline bool no_dense_exchange(int kind) { return is_dotset_kind(kind) || kind == CE_STATE_PNCOUNTER; }
+// planes of the dense state and batch (u64[planes * cap]): PNCounter keeps p at [slot] and n at
+// [slot + cap]; next_op_versions is one plane for every kind
+inline uint32_t state_planes(int kind) { return kind == CE_STATE_PNCOUNTER ? 2u : 1u; }
 }  // namespace ce
 
 namespace ce {
@@ -212,7 +218,8 @@ int resolve_host_parse(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs
                        bool outer);
 uint32_t host_gate(const uint32_t* fa, const uint64_t* fv, uint32_t n, std::vector<uint64_t>* expect,
                    uint8_t* apply);
-int merge_dots_host(ce_core* c, const Dots& dots);
+// neg (PNCounter): the dots of the n plane, merged in the same launch
+int merge_dots_host(ce_core* c, const Dots& dots, const Dots* neg = nullptr);
 // read_remote_ops over a batch resident in HBM (ce_core.cpp).  shard_hi (device, m + 1 words):
 // the sharded gate's windows and flags (ce_shard.hip) instead of the local gate; the batch is
 // then left pending (not committed) for ce_core_pending_commit.

@@ -536,4 +536,38 @@ __device__ __forceinline__ bool canon_dot(const uint32_t (&w)[12], uint32_t L, u
   return ok != 0;
 }
 
+// canonical rmp-serde pncounter::Op: 82 a3"dot" <canonical Dot> a3"dir" a3"Pos"|a3"Neg" -- 13
+// bytes around the Dot, so 47 + {0, 1, 2, 4, 8} by the counter's marker (at byte 38 of the op)
+static constexpr uint32_t kPnOpExtra = 13;
+__device__ __forceinline__ uint32_t pn_len_of_marker(uint32_t mk) {
+  const uint32_t d = dot_len_of_marker(mk);
+  return d ? d + kPnOpExtra : 0u;
+}
+
+// check one canonical Op of length L in the 56-byte window w (bytes cand..cand+55): the 5-byte
+// head, the canonical Dot at byte 5 (canon_dot on the window shifted by 5) and the 8-byte tail,
+// which starts at byte L - 8 = 39 + {0, 1, 2, 4, 8}; dir = 1 for Neg.  Branch-free, as canon_dot.
+__device__ __forceinline__ bool canon_pn_op(const uint32_t (&w)[14], uint32_t L, uint32_t& k0,
+                                            uint32_t& k1, uint32_t& k2, uint32_t& k3,
+                                            unsigned long long& ctr, uint32_t& dir) {
+  uint32_t dw[12];
+#pragma unroll
+  for (int i = 0; i < 12; i++) dw[i] = __builtin_amdgcn_alignbyte(w[i + 2], w[i + 1], 1);
+  const bool dot_ok = canon_dot(dw, L - kPnOpExtra, k0, k1, k2, k3, ctr);
+  // bytes 39..54 as four words, then the two tail words at byte 39 + t, t = L - 47
+  const uint32_t W0 = __builtin_amdgcn_alignbyte(w[10], w[9], 3), W1 = __builtin_amdgcn_alignbyte(w[11], w[10], 3);
+  const uint32_t W2 = __builtin_amdgcn_alignbyte(w[12], w[11], 3), W3 = __builtin_amdgcn_alignbyte(w[13], w[12], 3);
+  const uint32_t t = L - 47u, sel = t >> 2, sh = t & 3u;
+  const uint32_t a = sel == 0 ? W0 : sel == 1 ? W1 : W2;
+  const uint32_t b = sel == 0 ? W1 : sel == 1 ? W2 : W3;
+  const uint32_t c = sel == 0 ? W2 : W3;  // used only when sh != 0 (t = 1, 2: sel = 0)
+  const uint32_t t0 = __builtin_amdgcn_alignbyte(b, a, sh), t1 = __builtin_amdgcn_alignbyte(c, b, sh);
+  const uint32_t neg = (uint32_t)(t1 == 0x67654ea3u);  // a3 "Neg"
+  const uint32_t ok = (uint32_t)(w[0] == 0x6f64a382u) & (uint32_t)((w[1] & 0xffu) == 0x74u) &
+                      (uint32_t)(t0 == 0x726964a3u) & ((uint32_t)(t1 == 0x736f50a3u) | neg) &
+                      (uint32_t)dot_ok;
+  dir = neg;
+  return ok != 0;
+}
+
 }  // namespace ce

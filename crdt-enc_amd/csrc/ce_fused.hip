@@ -216,7 +216,11 @@ struct SupVers {
 // its read, 4 = one extra ChaCha20 block's double rounds spread over the fast rounds (one per
 // round, the rest after the loop), 8 = the same extra block after the decode loops (4 vs 8:
 // how much independent VALU work the decode's stalls could absorb)
-template <int LPF, int DOPT = 0, bool CARRY = false, typename Pf>
+// PN: the op grammar is Vec<pncounter::Op<Uuid>> (canon_pn_op / parse_pn_op) and a.batch holds two
+// planes, Pos at [slot] and Neg at [slot + mask + 1]; the fold index carries the plane, so the
+// pending (index, max), its carry and the flush are the Dot form's.  Every PN difference is an
+// `if constexpr`: the Dot instantiations compile the code they always did.
+template <int LPF, int DOPT = 0, bool CARRY = false, bool PN = false, typename Pf>
 __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& sup, const uint8_t* fl,
                                             uint32_t len, bool live, bool apply, uint32_t f,
                                             uint32_t grp, uint32_t sub, DecState& S, Pf&& prefetch) {
@@ -277,7 +281,8 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
   auto remember = [&](uint32_t slot, uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3) {
     if (slot != 0xffffffffu) { S.ck0 = k0; S.ck1 = k1; S.ck2 = k2; S.ck3 = k3; S.cslot = slot; }
   };
-  auto fold_dot = [&](uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, unsigned long long ctr) {
+  auto fold_dot = [&](uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, unsigned long long ctr,
+                      uint32_t dir = 0) {
     uint32_t slot;
     if (cached(k0, k1, k2, k3)) slot = S.cslot;
     else if (DOPT & 1) {
@@ -286,6 +291,9 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
     } else {
       slot = lookup_slot1(a.table, a.mask, a.nil_actor, k0, k1, k2, k3);
       remember(slot, k0, k1, k2, k3);
+    }
+    if constexpr (PN) {  // the direction selects the plane (the cache keeps the plain slot)
+      if (slot != 0xffffffffu) slot += dir * (a.mask + 1u);
     }
     fold_slot(slot, k0, k1, k2, k3, ctr);
   };
@@ -297,7 +305,8 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
   // goes on to the paths below from Dot 0, exactly as if this block were absent.  Mixed-actor
   // files stop after their first LPF Dots.  Folding the max counter of Dots that all name one
   // actor is what folding them one by one does (VClock::apply, crdt-enc/src/lib.rs:533-535).
-  {
+  // (Not built for PN: it would need one max per direction.)
+  if constexpr (!PN) {
     uint32_t L0 = 0;
     if (live && st == CE_OK && remaining > 1 && pos + 34 <= blen) L0 = dot_len_of_marker(body[pos + 33]);
     bool tp = L0 > 34u && (uint64_t)pos + remaining * L0 <= blen;
@@ -399,7 +408,58 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
   // A round takes two Dots per lane (done + sub and done + LPF + sub): their 26 LDS reads are in
   // flight together.  It stops at the first Dot that is not canonical with length L0 (nothing
   // past it is folded); the sequential loop below takes over from there.
-  {
+  if constexpr (PN) {
+    // the same rounds over canonical Ops: two per lane at the first Op's length, 15 aligned LDS
+    // dwords each -> the 56-byte window at the Op's byte shift
+    uint32_t L0 = 0;
+    if (live && st == CE_OK && remaining > 0 && pos + 39 <= blen) L0 = pn_len_of_marker(body[pos + 38]);
+    uint32_t done = 0;
+    bool fast = L0 != 0;
+    for (;;) {
+      const bool fb = fast && done < remaining;
+      if (!__any(fb)) break;
+      bool need[2], rd[2], valid[2];
+      uint32_t k0[2], k1[2], k2[2], k3[2], cand[2], dir[2];
+      unsigned long long ctr[2];
+      uint32_t dd[2][15];
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const uint32_t i = done + sub + LPF * h;
+        cand[h] = pos + i * L0;
+        need[h] = fb && i < remaining;
+        rd[h] = need[h] && cand[h] + L0 <= blen;
+        const uint32_t* d = reinterpret_cast<const uint32_t*>(body) + ((rd[h] ? cand[h] : 0u) >> 2);
+#pragma unroll
+        for (int q = 0; q < 15; q++) dd[h][q] = d[q];
+      }
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const uint32_t sh = cand[h] & 3;
+        uint32_t w[14];
+#pragma unroll
+        for (int q = 0; q < 14; q++) w[q] = __builtin_amdgcn_alignbyte(dd[h][q + 1], dd[h][q], sh);
+        valid[h] = canon_pn_op(w, L0, k0[h], k1[h], k2[h], k3[h], ctr[h], dir[h]) && rd[h];
+      }
+      const unsigned long long bad0 = grp_bits<LPF>(need[0] && !valid[0], grp);
+      const unsigned long long bad1 = grp_bits<LPF>(need[1] && !valid[1], grp);
+      const uint32_t kk = bad0 ? (uint32_t)__builtin_ctzll(bad0)
+                               : bad1 ? (uint32_t)LPF + (uint32_t)__builtin_ctzll(bad1) : 2u * LPF;
+      if (do_fold && need[0] && sub < kk) fold_dot(k0[0], k1[0], k2[0], k3[0], ctr[0], dir[0]);
+      if (do_fold && need[1] && LPF + sub < kk) fold_dot(k0[1], k1[1], k2[1], k3[1], ctr[1], dir[1]);
+      if (!pf_done) {
+        prefetch();
+        pf_done = true;
+      }
+      if (fb) {
+        const bool bad = (bad0 | bad1) != 0;
+        const uint64_t left = remaining - done;
+        done += bad ? kk : (uint32_t)(left < 2u * LPF ? left : 2u * LPF);
+        if (bad) fast = false;
+      }
+    }
+    pos += done * L0;
+    remaining -= done;
+  } else {
     uint32_t L0 = 0;
     if (live && st == CE_OK && remaining > 0 && pos + 34 <= blen) L0 = dot_len_of_marker(body[pos + 33]);
     uint32_t done = 0;
@@ -470,9 +530,25 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
     // starts only when every earlier Dot of the round had length Ls.
     bool valid = false;
     uint32_t Lme = 0;
-    uint32_t k0 = 0, k1 = 0, k2 = 0, k3 = 0;
+    uint32_t k0 = 0, k1 = 0, k2 = 0, k3 = 0, dir = 0;
     unsigned long long ctr = 0;
     const uint32_t cand = pos + sub * S.Ls;
+    if constexpr (PN) {
+      if (busy && sub < remaining && cand + 47 <= blen) {
+        const uint32_t* d = reinterpret_cast<const uint32_t*>(body) + (cand >> 2);
+        const uint32_t sh = cand & 3;
+        uint32_t dd[15];
+#pragma unroll
+        for (int i = 0; i < 15; i++) dd[i] = d[i];
+        uint32_t w[14];
+#pragma unroll
+        for (int i = 0; i < 14; i++) w[i] = __builtin_amdgcn_alignbyte(dd[i + 1], dd[i], sh);
+        Lme = pn_len_of_marker((w[9] >> 16) & 0xff);
+        const uint32_t L = sub == 0 ? Lme : S.Ls;
+        valid = ((uint32_t)canon_pn_op(w, L, k0, k1, k2, k3, ctr, dir) & (uint32_t)(Lme != 0) &
+                 (uint32_t)(cand + L <= blen)) != 0;
+      }
+    } else
     if (busy && sub < remaining && cand + 34 <= blen) {
       // 13 aligned LDS dwords -> the 48-byte window at cand
       const uint32_t* d = reinterpret_cast<const uint32_t*>(body) + (cand >> 2);
@@ -495,12 +571,12 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
     if (!m0 && k > 1) k = 1;  // lanes >= 1 read at the wrong offsets
     // next speculation: the first lane past the round sits exactly on the next Dot
     const uint32_t inf = m0 ? k : 0u;
-    const uint32_t code = sub == inf ? len_code(Lme) : 0u;
+    const uint32_t code = sub == inf ? len_code(PN ? Lme - kPnOpExtra : Lme) : 0u;
     const uint32_t nc = (grp_bits<LPF>(code & 1, grp) ? 1u : 0u) |
                         (grp_bits<LPF>(code & 2, grp) ? 2u : 0u) |
                         (grp_bits<LPF>(code & 4, grp) ? 4u : 0u);
     const uint32_t Lold = S.Ls;
-    if (nc) S.Ls = code_len(nc);  // when !m0 this is lane 0's own length
+    if (nc) S.Ls = code_len(nc) + (PN ? kPnOpExtra : 0u);  // when !m0 this is lane 0's own length
     // general grammar for one element (group leader), e.g. reordered keys / array form
     const bool general = busy && k == 0;
     bool fold_me = do_fold && busy && sub < k;
@@ -510,7 +586,8 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
       if (general && sub == 0) {
         Rd q{body, blen, pos};
         uint64_t aoff = 0, c = 0;
-        gok = parse_dot(q, &aoff, &c);
+        if constexpr (PN) gok = parse_pn_op(q, &aoff, &c, &dir);
+        else gok = parse_dot(q, &aoff, &c);
         if (gok == 1) {
           k0 = ld_le32(body + aoff); k1 = ld_le32(body + aoff + 4);
           k2 = ld_le32(body + aoff + 8); k3 = ld_le32(body + aoff + 12);
@@ -526,7 +603,7 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
         else { pos = npos; remaining -= 1; }
       }
     }
-    if (fold_me) fold_dot(k0, k1, k2, k3, ctr);
+    if (fold_me) fold_dot(k0, k1, k2, k3, ctr, dir);
     if (busy && k > 0) {
       pos += m0 ? k * Lold : S.Ls;  // !m0: k == 1 and Ls == lane 0's Dot length
       remaining -= k;
@@ -1542,7 +1619,9 @@ __device__ const uint32_t kPolyOne[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 // ----------------------------------------------------------------------------------------
 // PAIR: the lane's blocks' keystreams two at a time (chacha_block_pre2); EARLY: the next file's
 // parameters loaded when this one starts (a whole iteration of latency) instead of in the decode
-template <bool PAIR, bool EARLY>
+// PN: the decode's op grammar (decode_fold's PN; a.batch in two planes); the open is the same
+// code.  Only k_open_fold_v3<false, true, true> is built: a PNCounter core takes no alternate.
+template <bool PAIR, bool EARLY, bool PN = false>
 __global__ __launch_bounds__(64, 2)
 void k_open_fold_v3(DecodeArgs a) {
   constexpr int LPF = 16, F = 4, BPL = 4;
@@ -1557,7 +1636,7 @@ void k_open_fold_v3(DecodeArgs a) {
   uint32_t g = bcast((uint32_t)(((uint64_t)blockIdx.x * ngroups) / gridDim.x));
   FilePre2 nx = load_pre2(a, g * F + grp);
   const SupVers sup(a);
-  DecState S{38, 0, 0, 0, 0, 0xffffffffu};
+  DecState S{PN ? 51u : 38u, 0, 0, 0, 0, 0xffffffffu};
   AuthFails fails;
   // this lane's tree weight r^(4q), q = (sub + 15) & 15: X = r^(4 (q & 3)) in {1, r^4, r^8,
   // r^12}, Y = r^(16 (q >> 2)) in {1, r^16, r^32, r^48}, read from FileParams.rpow / PolyAux
@@ -1743,7 +1822,7 @@ void k_open_fold_v3(DecodeArgs a) {
     // 4) data-version check, decode from LDS, fold; the next iteration's parameters are loaded
     //    inside (their latency hides under the decode)
     if (CE_V3_PRIO) __builtin_amdgcn_s_setprio(CE_V3_PRIO);  // the decode's short dependent chains first
-    decode_fold<LPF, 0, true>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, S, [&] {
+    decode_fold<LPF, 0, true, PN>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, S, [&] {
       if (!EARLY) nx = load_pre2(a, (g + 1) * F + grp);
     });
     if (CE_V3_PRIO) __builtin_amdgcn_s_setprio(0);
@@ -2003,6 +2082,16 @@ hipError_t launch_open_small_v2(hipStream_t s, const DecodeArgs& a) {
   } else {
     launch_v2<16, 3, false, 1, false>(s, a);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_open_fold_pn(hipStream_t s, const DecodeArgs& a, hipEvent_t t0, hipEvent_t t1) {
+  if (a.n == 0) return hipSuccess;
+  if (!a.aux) return hipErrorInvalidValue;  // the v3 open needs the setup's PolyAux rows
+  static const uint32_t res = resident_blocks(k_open_fold_v3<false, true, true>, 64);
+  const dim3 grid(std::min<uint32_t>((a.n + 3) / 4, res));
+  if (t0) hipExtLaunchKernelGGL((k_open_fold_v3<false, true, true>), grid, dim3(64), 0, s, t0, t1, 0u, a);
+  else hipLaunchKernelGGL((k_open_fold_v3<false, true, true>), grid, dim3(64), 0, s, a);
   return hipGetLastError();
 }
 

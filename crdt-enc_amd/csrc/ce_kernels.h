@@ -165,6 +165,9 @@ struct DecodeArgs {
   const PolyAux* aux;           // fused open (k_open_fold_v3): the setup's per-file constants
 };
 hipError_t launch_decode_dots(hipStream_t s, const DecodeArgs& a, uint32_t grid_waves);
+// the same for a PNCounter core: Vec<pncounter::Op<Uuid>>, a.batch in two planes (Pos at [slot],
+// Neg at [slot + mask + 1])
+hipError_t launch_decode_pn_ops(hipStream_t s, const DecodeArgs& a, uint32_t grid_waves);
 // diagnostics: shader clock vs the reference clock (ce_ctx_clock_probe)
 hipError_t launch_clock_probe(hipStream_t s, unsigned long long* out, uint32_t blocks,
                               uint32_t samples, uint32_t ticks);
@@ -193,6 +196,10 @@ hipError_t launch_open_fold_small(hipStream_t s, const DecodeArgs& a, int files_
 // t0 / t1: timing events recorded by the dispatch itself (hipExtLaunchKernel), or none
 hipError_t launch_open_fold_v2(hipStream_t s, const DecodeArgs& a, int files_per_wave,
                                hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// the PNCounter form of the default fused kernel (k_open_fold_v3<false, true>'s geometry, the
+// only one this kind takes): needs a.aux
+hipError_t launch_open_fold_pn(hipStream_t s, const DecodeArgs& a, hipEvent_t t0 = nullptr,
+                               hipEvent_t t1 = nullptr);
 // open only: single-page files (<= kSmallMax) into a.pt at their out_off, 16 lanes per file
 // (k_open_fold_v2<..., DEC = false>); statuses and the failure counters as the segment pass sets them
 hipError_t launch_open_small_v2(hipStream_t s, const DecodeArgs& a);
@@ -225,11 +232,16 @@ hipError_t launch_nov_apply(hipStream_t s, unsigned long long* nov, const uint32
                             const unsigned long long* newnov, uint32_t m, const uint32_t* counters);
 // to_vec_named(StateWrapper<VClock|GCounter>) from the dense nov / state arrays (k sorted slots);
 // clear length -> offs[1] (offs[0] = 0).  Upper bound of the output: vclock_ser_bound(k)
+// pn_cap != 0: StateWrapper<PNCounter>, st in two planes of pn_cap words (p, then n): the state is
+// 82 a1"p" 81 a5"inner" <VClock> a1"n" 81 a5"inner" <VClock>, three maps with their own counts
 hipError_t launch_serialize_vclock(hipStream_t s, const unsigned long long* nov,
                                   const unsigned long long* st, const uint32_t* sorted, uint32_t k,
                                   const ActorSlot* table, bool gcounter, const uint8_t* prefix16,
-                                  uint8_t* out, unsigned long long* offs);
-inline uint64_t vclock_ser_bound(uint64_t k) { return 16 + 24 + 5 + 27 * k + 19 + 5 + 27 * k; }
+                                  uint8_t* out, unsigned long long* offs, uint32_t pn_cap = 0);
+inline uint64_t vclock_ser_bound(uint64_t k, bool pn = false) {
+  const uint64_t two = 16 + 24 + 5 + 27 * k + 19 + 5 + 27 * k;
+  return pn ? two + 3 + 15 + 5 + 27 * k : two;  // 82 a1"p" before "inner"; a1"n" .. "dots" <map> after p
+}
 
 // The compaction's prologue as one launch (instead of an 80-byte upload, two counter fills and
 // k_nov_apply): the seal's small arguments at `args` -- offs[2] = {0, (serializer)}, out_offs[1]

@@ -200,6 +200,7 @@ __global__ __launch_bounds__(256) void k_seal_setup(const uint8_t* __restrict__ 
 static constexpr int kWavesPerBlock = 4;
 static constexpr uint32_t kSegBytes = kSegBlocks * 16;
 
+template <bool PN = false>
 __device__ void decode_file(const DecodeArgs& a, uint32_t f, uint32_t lane);
 
 // the 48-byte window at pt + p (unaligned global loads)
@@ -648,6 +649,9 @@ __global__ __launch_bounds__(256) void k_finalize_multi(uint8_t* __restrict__ ou
 // decode + fold: one wavefront per file
 // ----------------------------------------------------------------------------------------
 // one wave decodes and folds file f front to back (the general path; k_decode_split's fallback)
+// PN: Vec<pncounter::Op<Uuid>> (canon_pn_op / parse_pn_op), folded into the plane its direction
+// names (Neg at slot + mask + 1); the Dot form compiles the code it always did
+template <bool PN>
 __device__ void decode_file(const DecodeArgs& a, uint32_t f, uint32_t lane) {
   {
     const FileParams* Pp = a.params + f;
@@ -671,12 +675,16 @@ __device__ void decode_file(const DecodeArgs& a, uint32_t f, uint32_t lane) {
     // at the end of the file one wave max when every lane holds the same slot
     uint32_t pslot = 0xffffffffu, cslot = 0xffffffffu, c0 = 0, c1 = 0, c2 = 0, c3 = 0;
     unsigned long long pbest = 0;
-    auto fold_dot = [&](uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, unsigned long long ctr) {
+    auto fold_dot = [&](uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, unsigned long long ctr,
+                        uint32_t dir = 0) {
       uint32_t slot;
       if (cslot != 0xffffffffu && k0 == c0 && k1 == c1 && k2 == c2 && k3 == c3) slot = cslot;
       else {
         slot = lookup_slot1(a.table, a.mask, a.nil_actor, k0, k1, k2, k3);
         if (slot != 0xffffffffu) { c0 = k0; c1 = k1; c2 = k2; c3 = k3; cslot = slot; }
+      }
+      if constexpr (PN) {
+        if (slot != 0xffffffffu) slot += dir * (a.mask + 1u);
       }
       if (slot == 0xffffffffu) {
         const uint32_t mi = atomicAdd(&a.counters[4], 1u);
@@ -703,8 +711,9 @@ __device__ void decode_file(const DecodeArgs& a, uint32_t f, uint32_t lane) {
       // A round reads 64 candidate Dots at pos + lane L.  L is speculated from the previous round
       // (the first round's from the marker), so the next round's loads are issued before this
       // round's fold; a round whose first Dot does not have length L re-reads the marker.
-      uint32_t L = remaining > 0 && pos + 34 <= blen ? dot_len_of_marker(body[pos + 33]) : 0;
-      uint4 A = make_uint4(0, 0, 0, 0), B = A, C = A;
+      uint32_t L = PN ? (remaining > 0 && pos + 39 <= blen ? pn_len_of_marker(body[pos + 38]) : 0)
+                      : (remaining > 0 && pos + 34 <= blen ? dot_len_of_marker(body[pos + 33]) : 0);
+      uint4 A = make_uint4(0, 0, 0, 0), B = A, C = A, D = A;
       auto load = [&](uint32_t p0, uint64_t rem) {
         const uint32_t cand = p0 + lane * L;
         const bool in = L != 0 && lane < rem && cand + L <= blen;
@@ -712,13 +721,20 @@ __device__ void decode_file(const DecodeArgs& a, uint32_t f, uint32_t lane) {
         A = *reinterpret_cast<const uint4*>(q);
         B = *reinterpret_cast<const uint4*>(q + 16);
         C = *reinterpret_cast<const uint4*>(q + 32);
+        if constexpr (PN) D = *reinterpret_cast<const uint4*>(q + 48);
         return in;
       };
       bool in = load(pos, remaining);
       while (remaining > 0 && st == CE_OK) {
         bool valid = false;
-        uint32_t k0 = 0, k1 = 0, k2 = 0, k3 = 0;
+        uint32_t k0 = 0, k1 = 0, k2 = 0, k3 = 0, dir = 0;
         unsigned long long ctr = 0;
+        if constexpr (PN) {
+          if (in) {
+            const uint32_t w[14] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w, C.x, C.y, C.z, C.w, D.x, D.y};
+            valid = canon_pn_op(w, L, k0, k1, k2, k3, ctr, dir);
+          }
+        } else
         if (in) {
           const uint32_t w[12] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w, C.x, C.y, C.z, C.w};
           valid = canon_dot(w, L, k0, k1, k2, k3, ctr);
@@ -731,10 +747,11 @@ __device__ void decode_file(const DecodeArgs& a, uint32_t f, uint32_t lane) {
           remaining -= k;
           const bool me = lane < k;
           in = load(pos, remaining);  // next round in flight while this one folds
-          if (do_fold && me) fold_dot(k0, k1, k2, k3, ctr);
+          if (do_fold && me) fold_dot(k0, k1, k2, k3, ctr, dir);
           continue;
         }
-        const uint32_t L2 = pos + 34 <= blen ? dot_len_of_marker(body[pos + 33]) : 0;
+        const uint32_t L2 = PN ? (pos + 39 <= blen ? pn_len_of_marker(body[pos + 38]) : 0)
+                               : (pos + 34 <= blen ? dot_len_of_marker(body[pos + 33]) : 0);
         if (L2 != 0 && L2 != L) {  // the Dot length changed: the same position, the new length
           L = L2;
           in = load(pos, remaining);
@@ -748,7 +765,8 @@ __device__ void decode_file(const DecodeArgs& a, uint32_t f, uint32_t lane) {
         if (lane == 0) {
           Rd q{body, blen, pos};
           uint64_t aoff = 0, c = 0;
-          ok = parse_dot(q, &aoff, &c);
+          if constexpr (PN) ok = parse_pn_op(q, &aoff, &c, &dir);
+          else ok = parse_dot(q, &aoff, &c);
           if (ok == 1) {
             g0 = ld_le32(body + aoff); g1 = ld_le32(body + aoff + 4);
             g2 = ld_le32(body + aoff + 8); g3 = ld_le32(body + aoff + 12);
@@ -759,10 +777,11 @@ __device__ void decode_file(const DecodeArgs& a, uint32_t f, uint32_t lane) {
         ok = __shfl(ok, 0);
         if (ok != 1) { st = CE_ERR_DECODE; break; }
         npos = bcast(npos);
-        if (do_fold && lane == 0) fold_dot(g0, g1, g2, g3, gc);
+        if (do_fold && lane == 0) fold_dot(g0, g1, g2, g3, gc, dir);
         pos = npos;
         remaining -= 1;
-        L = remaining > 0 && pos + 34 <= blen ? dot_len_of_marker(body[pos + 33]) : 0;
+        L = PN ? (remaining > 0 && pos + 39 <= blen ? pn_len_of_marker(body[pos + 38]) : 0)
+               : (remaining > 0 && pos + 34 <= blen ? dot_len_of_marker(body[pos + 33]) : 0);
         in = load(pos, remaining);
       }
       if (do_fold) {  // flush: one atomicMax per file when the lanes' pending slots agree
@@ -790,6 +809,35 @@ __device__ void decode_file(const DecodeArgs& a, uint32_t f, uint32_t lane) {
       atomicAdd(&a.counters[3], 1u);
       atomicMin(&a.counters[5], f);
     }
+  }
+}
+
+
+// k_decode_dots' work loop over Vec<pncounter::Op> files (a PNCounter core's multi-page files,
+// host-parse envelopes and multi-key retries); a.batch holds both planes
+__global__ __launch_bounds__(256) void k_decode_pn_ops(DecodeArgs a) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t stride = gridDim.x * kWavesPerBlock;
+  const uint32_t nwork = (a.large_only && !a.only) ? *((volatile uint32_t*)&a.counters[9]) : a.n;
+  if (a.large_only && !a.only) {
+    for (;;) {
+      uint32_t w = 0;
+      if (lane == 0) w = atomicAdd(&a.counters[15], 1u);
+      w = __shfl(w, 0);
+      if (w >= nwork) break;
+      const uint32_t f = bcast(a.large_list[w]);
+      const FileParams* Pp = a.params + f;
+      if (Pp->len <= kSmallMax || a.status[f] != CE_OK) continue;
+      decode_file<true>(a, f, lane);
+    }
+    return;
+  }
+  for (uint32_t w = bcast(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)); w < nwork; w += stride) {
+    const uint32_t f = w;
+    const FileParams* Pp = a.params + f;
+    if ((a.only && !a.only[f]) || (a.large_only && Pp->len <= kSmallMax)) continue;
+    if (a.status[f] != CE_OK) continue;
+    decode_file<true>(a, f, lane);
   }
 }
 
@@ -1139,12 +1187,15 @@ __device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t* ws, ui
   return pre + x - v;
 }
 
-template <int R>
+// PN (S = PNCounter<Uuid>): st holds two planes of pn_cap words, p then n, and the state is
+//   a5 "state" 82 a1 "p" 81 a5 "inner" 81 a4 "dots" <map n_p> {..} a1 "n" 81 a5 "inner" 81 a4 "dots" <map n_n> {..}
+// -- a third map with its own count, header width and scan; the two-map forms compile as before
+template <int R, bool PN = false>
 __global__ __launch_bounds__(1024) void k_serialize_vclock(
     const unsigned long long* __restrict__ nov, const unsigned long long* __restrict__ st,
     const uint32_t* __restrict__ sorted, uint32_t k, const ActorSlot* __restrict__ table,
     int gcounter, const uint8_t* __restrict__ prefix16, uint8_t* __restrict__ out,
-    unsigned long long* __restrict__ offs) {
+    unsigned long long* __restrict__ offs, uint32_t pn_cap) {
   __shared__ uint32_t ws[16];
   const uint32_t t = threadIdx.x;
   // R rounds per chunk held in registers: every load of a chunk is issued before any is used
@@ -1152,7 +1203,7 @@ __global__ __launch_bounds__(1024) void k_serialize_vclock(
   // registers also serve the write pass.
   const uint32_t rounds = (k + 1023) / 1024;
   uint32_t sl[R];
-  unsigned long long nv[R], sv[R];
+  unsigned long long nv[R], sv[R], qv[PN ? R : 1];
   auto load_chunk = [&](uint32_t r0) {
 #pragma unroll
     for (int r = 0; r < R; r++) {
@@ -1163,6 +1214,7 @@ __global__ __launch_bounds__(1024) void k_serialize_vclock(
     for (int r = 0; r < R; r++) {
       nv[r] = sl[r] != 0xffffffffu ? nov[sl[r]] : 0ull;
       sv[r] = sl[r] != 0xffffffffu ? st[sl[r]] : 0ull;
+      if constexpr (PN) qv[r] = sl[r] != 0xffffffffu ? st[sl[r] + pn_cap] : 0ull;
     }
   };
   // pass 1 (every workgroup, over all entries): entry counts and bytes of both maps, and the
@@ -1170,6 +1222,7 @@ __global__ __launch_bounds__(1024) void k_serialize_vclock(
   // they fit: <= 1024 R each)
   const uint32_t me = blockIdx.x;  // the round this workgroup writes
   uint32_t cnt = 0, bn = 0, bs = 0, pn = 0, ps = 0;
+  uint32_t cntq = 0, bq = 0, pq = 0;  // PN: the n plane's entries, their bytes, the bytes before this round
   for (uint32_t r0 = 0; r0 < rounds; r0 += R) {
     load_chunk(r0);
 #pragma unroll
@@ -1180,6 +1233,12 @@ __global__ __launch_bounds__(1024) void k_serialize_vclock(
       bn += ln;
       bs += ls;
       if (r0 + r < me) { pn += ln; ps += ls; }
+      if constexpr (PN) {
+        const uint32_t lq = qv[r] != 0 ? 18u + mp_uint_len(qv[r]) : 0u;
+        cntq += qv[r] != 0;
+        bq += lq;
+        if (r0 + r < me) pq += lq;
+      }
     }
   }
   uint32_t tc, tbn, tbs, tpn, tps;
@@ -1188,6 +1247,12 @@ __global__ __launch_bounds__(1024) void k_serialize_vclock(
   (void)block_scan_1024(bs, ws, &tbs);
   (void)block_scan_1024(pn, ws, &tpn);
   (void)block_scan_1024(ps, ws, &tps);
+  uint32_t cq = 0, tbq = 0, tpq = 0;
+  if constexpr (PN) {
+    (void)block_scan_1024(cntq, ws, &cq);  // a full count: exact whatever the rounds
+    (void)block_scan_1024(bq, ws, &tbq);
+    (void)block_scan_1024(pq, ws, &tpq);
+  }
   uint32_t cn = tc & 0xffff, cs = tc >> 16;
   if (rounds > R) {  // counts can pass 16 bits: recount exactly
     uint32_t a = 0, b = 0;
@@ -1202,7 +1267,40 @@ __global__ __launch_bounds__(1024) void k_serialize_vclock(
   const uint32_t pl = prefix16 ? 16u : 0u;
   const uint32_t nov_at = pl + 24 + mp_map_hdr_len(cn);                 // first nov entry
   const uint32_t st_hdr = nov_at + tbn;                                  // "state" ...
-  const uint32_t st_at = st_hdr + 6 + (gcounter ? 7u : 0u) + 6 + mp_map_hdr_len(cs);
+  // PN: "state" 82 a1"p" 81 a5"inner" 81 a4"dots" <map> = 6 + 1 + 2 + 7 + 6 before p's header
+  const uint32_t st_at = PN ? st_hdr + 22 + mp_map_hdr_len(cs)
+                            : st_hdr + 6 + (gcounter ? 7u : 0u) + 6 + mp_map_hdr_len(cs);
+  const uint32_t q_hdr = st_at + tbs;                                    // PN: a1"n" ...
+  const uint32_t q_at = q_hdr + 15 + mp_map_hdr_len(cq);                 // a1"n" 81 a5"inner" 81 a4"dots" <map>
+  if constexpr (PN) {
+    if (me == 0 && t == 0) {
+      uint8_t* o = out;
+      for (uint32_t i = 0; i < pl; i++) *o++ = prefix16[i];
+      *o++ = 0x82;
+      o += mp_put_str(o, "next_op_versions", 16);
+      *o++ = 0x81;
+      o += mp_put_str(o, "dots", 4);
+      o += mp_put_map_hdr(o, cn);
+      o = out + st_hdr;
+      o += mp_put_str(o, "state", 5);
+      *o++ = 0x82;
+      o += mp_put_str(o, "p", 1);
+      *o++ = 0x81;
+      o += mp_put_str(o, "inner", 5);
+      *o++ = 0x81;
+      o += mp_put_str(o, "dots", 4);
+      o += mp_put_map_hdr(o, cs);
+      o = out + q_hdr;
+      o += mp_put_str(o, "n", 1);
+      *o++ = 0x81;
+      o += mp_put_str(o, "inner", 5);
+      *o++ = 0x81;
+      o += mp_put_str(o, "dots", 4);
+      o += mp_put_map_hdr(o, cq);
+      offs[0] = 0;
+      offs[1] = q_at + tbq;
+    }
+  } else
   if (me == 0 && t == 0) {
     uint8_t* o = out;
     for (uint32_t i = 0; i < pl; i++) *o++ = prefix16[i];
@@ -1259,12 +1357,22 @@ __global__ __launch_bounds__(1024) void k_serialize_vclock(
     const unsigned long long vs = slot != 0xffffffffu ? st[slot] : 0ull;
     const uint32_t ln = vn != 0 ? 18u + mp_uint_len(vn) : 0u;
     const uint32_t ls = vs != 0 ? 18u + mp_uint_len(vs) : 0u;
+    unsigned long long vq = 0;
+    uint32_t lq = 0;
+    if constexpr (PN) {
+      vq = slot != 0xffffffffu ? st[slot + pn_cap] : 0ull;
+      lq = vq != 0 ? 18u + mp_uint_len(vq) : 0u;
+    }
     ActorSlot a;
-    if (ln | ls) a = table[slot];
+    if (ln | ls | lq) a = table[slot];
     uint32_t tot;
     const uint32_t at = block_scan_1024(ln | (ls << 16), ws, &tot);
     if (ln) put(nov_at + tpn + (at & 0xffff), a, vn);
     if (ls) put(st_at + tps + (at >> 16), a, vs);
+    if constexpr (PN) {
+      const uint32_t atq = block_scan_1024(lq, ws, &tot);
+      if (lq) put(q_at + tpq + atq, a, vq);
+    }
   }
 }
 
@@ -1405,6 +1513,13 @@ hipError_t launch_decode_dots(hipStream_t s, const DecodeArgs& a, uint32_t grid_
   if (a.n == 0) return hipSuccess;
   const uint32_t blocks = (grid_waves + kWavesPerBlock - 1) / kWavesPerBlock;
   hipLaunchKernelGGL(k_decode_dots, dim3(blocks), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_decode_pn_ops(hipStream_t s, const DecodeArgs& a, uint32_t grid_waves) {
+  if (a.n == 0) return hipSuccess;
+  const uint32_t blocks = (grid_waves + kWavesPerBlock - 1) / kWavesPerBlock;
+  hipLaunchKernelGGL(k_decode_pn_ops, dim3(blocks), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
@@ -1593,11 +1708,16 @@ hipError_t launch_state_heads(hipStream_t s, const FileParams* params, const int
 hipError_t launch_serialize_vclock(hipStream_t s, const unsigned long long* nov,
                                   const unsigned long long* st, const uint32_t* sorted, uint32_t k,
                                   const ActorSlot* table, bool gcounter, const uint8_t* prefix16,
-                                  uint8_t* out, unsigned long long* offs) {
+                                  uint8_t* out, unsigned long long* offs, uint32_t pn_cap) {
   // one workgroup per 1024 sorted entries (at least one: the headers)
   const uint32_t rounds = k ? (k + 1023) / 1024 : 1;
+  if (pn_cap) {
+    hipLaunchKernelGGL((k_serialize_vclock<2, true>), dim3(rounds), dim3(1024), 0, s, nov, st, sorted, k, table,
+                       0, prefix16, out, offs, pn_cap);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(k_serialize_vclock<4>, dim3(rounds), dim3(1024), 0, s, nov, st, sorted, k, table,
-                     gcounter ? 1 : 0, prefix16, out, offs);
+                     gcounter ? 1 : 0, prefix16, out, offs, 0u);
   return hipGetLastError();
 }
 

@@ -256,7 +256,7 @@ int ce_core_ingest_ops_device_sharded(ce_core* c, const uint8_t* d_blob, const u
                                       uint64_t blob_len, const uint8_t* actors, uint32_t m,
                                       const uint32_t* d_fa, const uint64_t* d_fv, const uint64_t* d_hi,
                                       int32_t* status) {
-  if (!c || (n && (!d_blob || !d_offs || !d_fa || !d_fv)) || (m && !actors) || !d_hi || is_dotset_kind(c->kind))
+  if (!c || (n && (!d_blob || !d_offs || !d_fa || !d_fv)) || (m && !actors) || !d_hi || no_dense_exchange(c->kind))
     return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
   (void)hipSetDevice(c->ctx->device);
@@ -285,7 +285,7 @@ int ce_core_ingest_ops_device_sharded(ce_core* c, const uint8_t* d_blob, const u
 }
 
 int ce_core_pending_export(ce_core* c, uint64_t* d_batch, uint64_t cap_words, int* ready) {
-  if (!c || !d_batch || !ready || is_dotset_kind(c->kind)) return CE_ERR_INVALID_ARG;
+  if (!c || !d_batch || !ready || no_dense_exchange(c->kind)) return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
   if (!c->pending || c->pending_gen != c->table_gen) return c->ctx->fail(CE_ERR_INVALID_ARG, "no pending batch");
   // an actor outside the registered slots (the ingest inserted it, and may have grown the table
@@ -300,7 +300,7 @@ int ce_core_pending_export(ce_core* c, uint64_t* d_batch, uint64_t cap_words, in
 }
 
 int ce_core_pending_commit(ce_core* c, int accept, const uint64_t* d_import, uint64_t import_words) {
-  if (!c || is_dotset_kind(c->kind)) return CE_ERR_INVALID_ARG;
+  if (!c || no_dense_exchange(c->kind)) return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
   (void)hipSetDevice(c->ctx->device);
   if (!c->pending) return c->ctx->fail(CE_ERR_INVALID_ARG, "no pending batch");

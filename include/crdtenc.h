@@ -204,7 +204,16 @@ enum ce_state_kind {
                             members}}; entries/deferred serialized in canonical order (members
                             ascending, deferred clocks by their msgpack bytes): the reference's
                             HashMap order is random                           */
-  CE_STATE_MVREG = 3     /* MVReg<u64, Uuid>: op = mvreg::Op::Put{clock, val}                 */
+  CE_STATE_MVREG = 3,    /* MVReg<u64, Uuid>: op = mvreg::Op::Put{clock, val}                 */
+  CE_STATE_PNCOUNTER = 4 /* PNCounter<Uuid> {p, n: GCounter}: op = pncounter::Op {dot, dir: Pos |
+                            Neg}.  Every ce_core_* entry point that takes a GCounter core takes
+                            this kind with the same contract, except the dense multi-GPU
+                            exchange: ce_core_dense_ready returns 0, and ce_core_export_dense,
+                            ce_core_import_dense, ce_core_ingest_ops_device_sharded,
+                            ce_core_pending_export and ce_core_pending_commit return
+                            CE_ERR_INVALID_ARG and touch nothing (ce_core_export_columns_device
+                            as for any non-Orswot kind).  Ranks exchange
+                            ce_core_state_bytes_device / ce_core_merge_state_device instead.     */
 };
 
 enum ce_open_flags {
