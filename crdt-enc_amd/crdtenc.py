@@ -631,7 +631,12 @@ class Core:
 
     def close(self):
         if self.p:
-            lib().ce_core_close(self.p)
+            # A context and its cores that become garbage together (a frame that held both) are
+            # finalized in any order, after the collector has emptied the context's WeakSet: a
+            # context destroyed first leaves the core's ce_ctx dangling, and ce_core_close
+            # would synchronize its stream.  The core's host memory is then left to the process.
+            if self.ctx.p:
+                lib().ce_core_close(self.p)
             self.p = ctypes.c_void_p()
 
     def __del__(self):

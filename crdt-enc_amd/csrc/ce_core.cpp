@@ -903,22 +903,24 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
   }
 
   // 2) GPU: single-page files: open + decode + fold fused; larger files: segments + decode
+  ctx->open_log.grid_cap = test_grid_cap();
   auto run_fold = [&](const uint8_t* only) -> int {
     da.only = only;
     da.large_only = 1;
     if (pnc) {  // always the default geometry's PNCounter form (no env-selected alternates)
       hipEvent_t t0, t1;
       (void)ctx->tlaunch("open_fold_small", &t0, &t1);
-      if ((e = launch_open_fold_pn(ctx->stream, da, t0, t1))) return ctx->hip_fail(e, "fused");
+      if ((e = launch_open_fold_pn(ctx->stream, da, ctx->open_log, t0, t1))) return ctx->hip_fail(e, "fused");
     } else if (c->fused == 2 && c->files_per_wave != 1) {
       hipEvent_t t0, t1;
       (void)ctx->tlaunch("open_fold_small", &t0, &t1);
-      if ((e = launch_open_fold_v2(ctx->stream, da, c->files_per_wave, t0, t1))) return ctx->hip_fail(e, "fused");
+      if ((e = launch_open_fold_v2(ctx->stream, da, c->files_per_wave, ctx->open_log, t0, t1))) return ctx->hip_fail(e, "fused");
     } else {
       const int t = ctx->tbegin("open_fold_small");
-      if ((e = launch_open_fold_small(ctx->stream, da, c->files_per_wave))) return ctx->hip_fail(e, "fused");
+      if ((e = launch_open_fold_small(ctx->stream, da, c->files_per_wave, ctx->open_log))) return ctx->hip_fail(e, "fused");
       ctx->tend(t);
     }
+    count_open_launches(c, ctx);
     if (!setup_known) {  // landed long ago: the fused kernel follows it
       if (hsetup_dev) {
         volatile const uint32_t* hp = hsetup;

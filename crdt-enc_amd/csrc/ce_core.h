@@ -131,6 +131,14 @@ struct ce_core {
 };
 
 namespace ce {
+// the open kernels ctx's launchers took since the last call -> c's path counts
+inline void count_open_launches(ce_core* c, ce_ctx* ctx) {
+  for (uint32_t i = 0; i < ctx->open_log.n; i++) c->path_counts[ctx->open_log.took[i]]++;
+  ctx->open_log.n = 0;
+}
+}  // namespace ce
+
+namespace ce {
 
 // msgpack writer (rmp-serde to_vec_named)
 struct Wr {

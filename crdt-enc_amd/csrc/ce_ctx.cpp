@@ -62,9 +62,16 @@ DevKey dev_key(const KeyRef& k) {
   return d;
 }
 
+uint32_t test_grid_cap() {
+  const char* e = getenv("CE_TEST_GRID_CAP");
+  const long v = e ? atol(e) : 0;
+  return v < 1 ? 0u : (uint32_t)std::min<long>(v, 1l << 30);
+}
+
 uint32_t grid_waves_for(uint32_t work) {
   // 256 CUs x 32 resident waves (segment kernel: <= 64 VGPRs -> 8 waves / SIMD)
-  const uint32_t full = 256u * 32u;
+  uint32_t full = 256u * 32u;
+  if (const uint32_t cap = test_grid_cap()) full = std::min(full, cap);
   return std::max<uint32_t>(1, std::min<uint32_t>(work, full));
 }
 
@@ -158,6 +165,7 @@ int device_open(ce_ctx* ctx, const uint8_t* d_blob, const uint64_t* d_offs, uint
     return ctx->hip_fail(e, "open setup");
   ctx->tend(t);
   if (small_lanes) {
+    ctx->open_log.grid_cap = test_grid_cap();
     DecodeArgs da{};
     da.pt = d_out;
     da.blob = d_blob;
@@ -174,7 +182,7 @@ int device_open(ce_ctx* ctx, const uint8_t* d_blob, const uint64_t* d_offs, uint
       da.mask = ds->mask;
     }
     t = ctx->tbegin("open_small");
-    if ((e = launch_open_small_v2(ctx->stream, da)) != hipSuccess) return ctx->hip_fail(e, "open small");
+    if ((e = launch_open_small_v2(ctx->stream, da, ctx->open_log)) != hipSuccess) return ctx->hip_fail(e, "open small");
     ctx->tend(t);
   }
   t = ctx->tbegin("segments_open");

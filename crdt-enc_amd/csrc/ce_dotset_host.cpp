@@ -1223,6 +1223,7 @@ int ds_ingest_ops(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uin
   if ((rc = device_open(ctx, d_blob, d_offs, n, blob_len, true, key_of(c), ctx->out.as<uint8_t>(),
                         ctx->status.as<int32_t>(), false, true, fused ? &fz : nullptr)))
     return rc;
+  count_open_launches(c, ctx);
   // 2) version gate -> apply flags (decode errors reject the batch whatever the gate says),
   // 3) data version + Vec<S::Op> decode, count pass, 4) bases: one exclusive scan over the kCntN
   // count columns back to back (the emit subtracts each column's first base), then one block for

@@ -875,20 +875,20 @@ static uint32_t resident_blocks(K kernel, int threads) {
   return (uint32_t)(per_cu * cus);
 }
 
-hipError_t launch_open_fold_small(hipStream_t s, const DecodeArgs& a, int files_per_wave) {
+hipError_t launch_open_fold_small(hipStream_t s, const DecodeArgs& a, int files_per_wave, OpenLaunchLog& log) {
   if (a.n == 0) return hipSuccess;
   static const uint32_t res16 = resident_blocks(k_open_fold_small<16>, 128);
   static const uint32_t res32 = resident_blocks(k_open_fold_small<32>, 256);
   static const uint32_t res64 = resident_blocks(k_open_fold_small<64>, 256);
   const uint32_t groups = (a.n + files_per_wave - 1) / files_per_wave;
   if (files_per_wave == 4) {
-    const uint32_t blocks = std::min<uint32_t>((groups + 1) / 2, res16);
+    const uint32_t blocks = log.grid(std::min<uint32_t>((groups + 1) / 2, res16), "open_small_lpf16");
     hipLaunchKernelGGL(k_open_fold_small<16>, dim3(blocks), dim3(128), 0, s, a);
   } else if (files_per_wave == 2) {
-    const uint32_t blocks = std::min<uint32_t>((groups + 3) / 4, res32);
+    const uint32_t blocks = log.grid(std::min<uint32_t>((groups + 3) / 4, res32), "open_small_lpf32");
     hipLaunchKernelGGL(k_open_fold_small<32>, dim3(blocks), dim3(256), 0, s, a);
   } else {
-    const uint32_t blocks = std::min<uint32_t>((groups + 3) / 4, res64);
+    const uint32_t blocks = log.grid(std::min<uint32_t>((groups + 3) / 4, res64), "open_small_lpf64");
     hipLaunchKernelGGL(k_open_fold_small<64>, dim3(blocks), dim3(256), 0, s, a);
   }
   return hipGetLastError();
@@ -2041,10 +2041,11 @@ void k_open_ds8(DecodeArgs a) {
 }
 
 template <int LPF, int W, bool JIT, int OPT = 3, bool DEC = true, bool DS = false>
-static void launch_v2(hipStream_t s, const DecodeArgs& a, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
+static void launch_v2(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log, const char* key,
+                      hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
   static const uint32_t res = resident_blocks(k_open_fold_v2<LPF, W, JIT, OPT, DEC, DS>, 64);
   const uint32_t groups = (a.n + 64 / LPF - 1) / (64 / LPF);
-  const dim3 grid(std::min<uint32_t>(groups, res));
+  const dim3 grid(log.grid(std::min<uint32_t>(groups, res), key));
   if (t0) {  // the launch's own start / end timestamps: no marker packets around the kernel
     hipExtLaunchKernelGGL((k_open_fold_v2<LPF, W, JIT, OPT, DEC, DS>), grid, dim3(64), 0, s, t0, t1, 0u, a);
   } else {
@@ -2054,7 +2055,7 @@ static void launch_v2(hipStream_t s, const DecodeArgs& a, hipEvent_t t0 = nullpt
 
 // single-page files opened into HBM (a.pt at each file's out_off), lane-owned ChaCha20 blocks;
 // a.only / a.apply unused.  Larger files: k_segments with skip_small (their setup's list).
-hipError_t launch_open_small_v2(hipStream_t s, const DecodeArgs& a) {
+hipError_t launch_open_small_v2(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log) {
   if (a.n == 0) return hipSuccess;
   // The DS form: 8 lanes per file for files of at most kDsFuseRegion bytes (k_open_ds8, with the
   // setup's PolyAux), then the 16-lane DS form over the files it left (a.only = big; it returns
@@ -2069,34 +2070,37 @@ hipError_t launch_open_small_v2(hipStream_t s, const DecodeArgs& a) {
     static const bool pf = !(getenv("CE_DS8_PF") && atoi(getenv("CE_DS8_PF")) == 0);
     if (pf) {
       static const uint32_t res = resident_blocks(k_open_ds8<true>, 64);
-      hipLaunchKernelGGL(k_open_ds8<true>, dim3(std::min<uint32_t>((a.n + 7) / 8, res)), dim3(64), 0, s, a);
+      const dim3 grid(log.grid(std::min<uint32_t>((a.n + 7) / 8, res), "open_ds8_pf"));
+      hipLaunchKernelGGL(k_open_ds8<true>, grid, dim3(64), 0, s, a);
     } else {
       static const uint32_t res = resident_blocks(k_open_ds8<false>, 64);
-      hipLaunchKernelGGL(k_open_ds8<false>, dim3(std::min<uint32_t>((a.n + 7) / 8, res)), dim3(64), 0, s, a);
+      const dim3 grid(log.grid(std::min<uint32_t>((a.n + 7) / 8, res), "open_ds8_nopf"));
+      hipLaunchKernelGGL(k_open_ds8<false>, grid, dim3(64), 0, s, a);
     }
     DecodeArgs b = a;
     b.only = a.ds.big;
-    launch_v2<16, 3, false, 1, false, true>(s, b);
+    launch_v2<16, 3, false, 1, false, true>(s, b, log, "open_ds16");
   } else if (a.ds.on) {
-    launch_v2<16, 3, false, 1, false, true>(s, a);
+    launch_v2<16, 3, false, 1, false, true>(s, a, log, "open_ds16");
   } else {
-    launch_v2<16, 3, false, 1, false>(s, a);
+    launch_v2<16, 3, false, 1, false>(s, a, log, "open_only_lpf16");
   }
   return hipGetLastError();
 }
 
-hipError_t launch_open_fold_pn(hipStream_t s, const DecodeArgs& a, hipEvent_t t0, hipEvent_t t1) {
+hipError_t launch_open_fold_pn(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log, hipEvent_t t0,
+                               hipEvent_t t1) {
   if (a.n == 0) return hipSuccess;
   if (!a.aux) return hipErrorInvalidValue;  // the v3 open needs the setup's PolyAux rows
   static const uint32_t res = resident_blocks(k_open_fold_v3<false, true, true>, 64);
-  const dim3 grid(std::min<uint32_t>((a.n + 3) / 4, res));
+  const dim3 grid(log.grid(std::min<uint32_t>((a.n + 3) / 4, res), "open_v3_pn"));
   if (t0) hipExtLaunchKernelGGL((k_open_fold_v3<false, true, true>), grid, dim3(64), 0, s, t0, t1, 0u, a);
   else hipLaunchKernelGGL((k_open_fold_v3<false, true, true>), grid, dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
-hipError_t launch_open_fold_v2(hipStream_t s, const DecodeArgs& a, int files_per_wave, hipEvent_t t0,
-                               hipEvent_t t1) {
+hipError_t launch_open_fold_v2(hipStream_t s, const DecodeArgs& a, int files_per_wave, OpenLaunchLog& log,
+                               hipEvent_t t0, hipEvent_t t1) {
   if (a.n == 0) return hipSuccess;
   // the v3 Poly1305 form (needs the setup's PolyAux rows); CE_FUSED_V2=1 keeps v2 for A/B
   static const bool force_v2 = getenv("CE_FUSED_V2") != nullptr;
@@ -2107,17 +2111,17 @@ hipError_t launch_open_fold_v2(hipStream_t s, const DecodeArgs& a, int files_per
       const char* e = getenv("CE_V3");
       return e ? atoi(e) : 2;
     }();
-    auto go = [&](auto kern) {
+    auto go = [&](auto kern, const char* key) {
       const uint32_t res = resident_blocks(kern, 64);
-      const dim3 grid(std::min<uint32_t>((a.n + 3) / 4, res));
+      const dim3 grid(log.grid(std::min<uint32_t>((a.n + 3) / 4, res), key));
       if (t0) hipExtLaunchKernelGGL(kern, grid, dim3(64), 0, s, t0, t1, 0u, a);
       else hipLaunchKernelGGL(kern, grid, dim3(64), 0, s, a);
     };
     switch (v3 & 3) {
-      case 1: go(k_open_fold_v3<true, false>); break;
-      case 2: go(k_open_fold_v3<false, true>); break;
-      case 3: go(k_open_fold_v3<true, true>); break;
-      default: go(k_open_fold_v3<false, false>); break;
+      case 1: go(k_open_fold_v3<true, false>, "open_v3_p1e0"); break;
+      case 2: go(k_open_fold_v3<false, true>, "open_v3_p0e1"); break;
+      case 3: go(k_open_fold_v3<true, true>, "open_v3_p1e1"); break;
+      default: go(k_open_fold_v3<false, false>, "open_v3_p0e0"); break;
     }
     return hipGetLastError();
   }
@@ -2136,34 +2140,34 @@ hipError_t launch_open_fold_v2(hipStream_t s, const DecodeArgs& a, int files_per
     return e ? atoi(e) : 1;
   }();
   if (files_per_wave == 2) {
-    if (w == 4) launch_v2<32, 4, false>(s, a, t0, t1);
-    else launch_v2<32, 3, false>(s, a, t0, t1);
+    if (w == 4) launch_v2<32, 4, false>(s, a, log, "open_v2_lpf32", t0, t1);
+    else launch_v2<32, 3, false>(s, a, log, "open_v2_lpf32", t0, t1);
   } else {
-    if (w == 3) launch_v2<16, 3, false>(s, a, t0, t1);
-    else if (w == 13) launch_v2<16, 3, true>(s, a, t0, t1);
-    else if (w == 12) launch_v2<16, 2, true>(s, a, t0, t1);
-    else if (opt == 0) launch_v2<16, 2, false, 0>(s, a, t0, t1);
-    else if (opt == 1) launch_v2<16, 2, false, 1>(s, a, t0, t1);
-    else if (opt == 2) launch_v2<16, 2, false, 2>(s, a, t0, t1);
-    else if (opt == 5) launch_v2<16, 2, false, 5>(s, a, t0, t1);
-    else if (opt == 9) launch_v2<16, 2, false, 9>(s, a, t0, t1);
-    else if (opt == 17) launch_v2<16, 2, false, 17>(s, a, t0, t1);
-    else if (opt == 21) launch_v2<16, 2, false, 21>(s, a, t0, t1);
-    else if (opt == 33) launch_v2<16, 2, false, 33>(s, a, t0, t1);
-    else if (opt == 65) launch_v2<16, 2, false, 65>(s, a, t0, t1);
-    else if (opt == 129) launch_v2<16, 2, false, 129>(s, a, t0, t1);
-    else if (opt == 257) launch_v2<16, 2, false, 257>(s, a, t0, t1);
-    else if (opt == 385) launch_v2<16, 2, false, 385>(s, a, t0, t1);
-    else if (opt == 513) launch_v2<16, 2, false, 513>(s, a, t0, t1);
-    else if (opt == 1025) launch_v2<16, 2, false, 1025>(s, a, t0, t1);
-    else if (opt == 81) launch_v2<16, 2, false, 81>(s, a, t0, t1);
-    else launch_v2<16, 2, false, 3>(s, a, t0, t1);
+    if (w == 3) launch_v2<16, 3, false>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (w == 13) launch_v2<16, 3, true>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (w == 12) launch_v2<16, 2, true>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 0) launch_v2<16, 2, false, 0>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 1) launch_v2<16, 2, false, 1>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 2) launch_v2<16, 2, false, 2>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 5) launch_v2<16, 2, false, 5>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 9) launch_v2<16, 2, false, 9>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 17) launch_v2<16, 2, false, 17>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 21) launch_v2<16, 2, false, 21>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 33) launch_v2<16, 2, false, 33>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 65) launch_v2<16, 2, false, 65>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 129) launch_v2<16, 2, false, 129>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 257) launch_v2<16, 2, false, 257>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 385) launch_v2<16, 2, false, 385>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 513) launch_v2<16, 2, false, 513>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 1025) launch_v2<16, 2, false, 1025>(s, a, log, "open_v2_lpf16", t0, t1);
+    else if (opt == 81) launch_v2<16, 2, false, 81>(s, a, log, "open_v2_lpf16", t0, t1);
+    else launch_v2<16, 2, false, 3>(s, a, log, "open_v2_lpf16", t0, t1);
   }
 #else
   // product: the measured default only -- SDWA rot16 on, next-ciphertext prefetch off (same-box
   // A/B r02); 2 files per wave at a 3-wave budget (SDWA rot16 + prefetch) for the fpw = 2 geometry
-  if (files_per_wave == 2) launch_v2<32, 3, false, 3>(s, a, t0, t1);
-  else launch_v2<16, 2, false, 1>(s, a, t0, t1);
+  if (files_per_wave == 2) launch_v2<32, 3, false, 3>(s, a, log, "open_v2_lpf32", t0, t1);
+  else launch_v2<16, 2, false, 1>(s, a, log, "open_v2_lpf16", t0, t1);
 #endif
   return hipGetLastError();
 }

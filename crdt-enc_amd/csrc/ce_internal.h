@@ -150,6 +150,8 @@ struct ce_ctx {
   ce::DevBuf params, status, counters, extra, multi, partials, large, out, apply, refold, miss,
       supported, blob, offs, nonces, out_offs, outer_ver, batch_counters, split, segrec, redo, heads,
       poly_aux;  // PolyAux rows of the fused open (device_open_setup)
+  // which open kernels the last launches took (ce_kernels.h); drained into a core's path counts
+  ce::OpenLaunchLog open_log;
   ce::HostBuf h_counters, h_apply, h_stage, h_stage2, h_heads;
   uint32_t publish_gen = 0;  // k_publish_words generations (the setup's counters, C2 path)
   // marks the setup kernel's counter snapshot (h_counters + 128) as landed on the host
@@ -265,6 +267,10 @@ int seal_one(ce_ctx* ctx, const KeyRef& key, const uint8_t* outer_version, const
              const uint8_t* prefix16 = nullptr);
 
 uint32_t grid_waves_for(uint32_t work);
+// CE_TEST_GRID_CAP=<blocks> (tests only; 0 when absent or < 1): clamps the grids of the fused
+// open launchers (OpenLaunchLog.grid_cap) and grid_waves_for, so that a small batch runs every
+// persistent loop many times per wave.  Read per call, as CE_SEGDEC and CE_SPLIT.
+uint32_t test_grid_cap();
 
 // ce_dma.cpp: device -> host copies on an SDMA engine (HSA), completion on a signal
 struct DmaD2H {

@@ -189,20 +189,40 @@ hipError_t launch_segments_decode(hipStream_t s, const uint8_t* in, uint8_t* out
 hipError_t launch_segdec_apply(hipStream_t s, const DecodeArgs& a, SegScratch sc, const uint4* rec,
                                uint32_t n_large);
 
+// What the launch_open_* functions below did, for the host to count (ce_core_path_count): one key
+// per kernel launched ("open_v3_p0e1", "open_ds8_pf", ...; static strings), and "open_grid_capped"
+// for each grid that grid_cap reduced.  grid_cap (0: none) is the test-only CE_TEST_GRID_CAP, set
+// by the caller per ingest: every kernel here partitions its work for any gridDim, so a small
+// grid makes each wave run its persistent loop many times over a small batch.
+struct OpenLaunchLog {
+  uint32_t grid_cap = 0;
+  uint32_t n = 0;
+  const char* took[8];
+  void note(const char* key) {
+    if (n < 8) took[n++] = key;
+  }
+  uint32_t grid(uint32_t blocks, const char* key) {
+    note(key);
+    if (grid_cap == 0 || blocks <= grid_cap) return blocks;
+    note("open_grid_capped");
+    return grid_cap;
+  }
+};
+
 // fused open + decode + fold of single-page files (ce_fused.hip); files_per_wave in {1, 2, 4}
-hipError_t launch_open_fold_small(hipStream_t s, const DecodeArgs& a, int files_per_wave);
+hipError_t launch_open_fold_small(hipStream_t s, const DecodeArgs& a, int files_per_wave, OpenLaunchLog& log);
 // the same with whole ChaCha20 blocks per lane (keystream XOR in registers; ce_fused.hip
 // k_open_fold_v2); files_per_wave in {2, 4}
 // t0 / t1: timing events recorded by the dispatch itself (hipExtLaunchKernel), or none
-hipError_t launch_open_fold_v2(hipStream_t s, const DecodeArgs& a, int files_per_wave,
+hipError_t launch_open_fold_v2(hipStream_t s, const DecodeArgs& a, int files_per_wave, OpenLaunchLog& log,
                                hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 // the PNCounter form of the default fused kernel (k_open_fold_v3<false, true>'s geometry, the
 // only one this kind takes): needs a.aux
-hipError_t launch_open_fold_pn(hipStream_t s, const DecodeArgs& a, hipEvent_t t0 = nullptr,
-                               hipEvent_t t1 = nullptr);
+hipError_t launch_open_fold_pn(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log,
+                               hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 // open only: single-page files (<= kSmallMax) into a.pt at their out_off, 16 lanes per file
 // (k_open_fold_v2<..., DEC = false>); statuses and the failure counters as the segment pass sets them
-hipError_t launch_open_small_v2(hipStream_t s, const DecodeArgs& a);
+hipError_t launch_open_small_v2(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log);
 
 // version gate on the device (ce_fused.hip): files grouped by actor with consecutive versions
 // (Storage::load_ops order, storage.rs:36-40) -> apply flags, first gap, next versions.

@@ -15,6 +15,7 @@ import pytest
 
 import crdtenc
 import dotset_gen as G
+from wave_run_corpus import _canonical_orswot
 from oracle import crdts as C
 
 pytestmark = pytest.mark.gpu
@@ -1268,29 +1269,6 @@ def test_scan_forms_equal(ctx):
         assert r.returncode == 0, r.stderr[-2000:]
         outs[mode] = r.stdout.strip().splitlines()[-1]
     assert outs["two"] == outs["three"] == want, outs
-
-
-def _canonical_orswot(rng, actors, n_versions, ops_per_file, members, widths=(1, 2, 3, 5, 9), p_rm=0.2):
-    """Op files whose ops are all the forms the open's decode proves: one-member Adds of the
-    writer's own dots, removals with a one-entry clock {writer: an earlier counter}; counters and
-    members drawn from every msgpack uint width (fixint, cc, cd, ce, cf)."""
-    lim = {1: (0, 127), 2: (128, 255), 3: (256, 65535), 5: (65536, (1 << 32) - 1), 9: (1 << 32, (1 << 64) - 1)}
-    files = {a: [] for a in actors}
-    ctr = {a: 0 for a in actors}
-    for _ in range(n_versions):
-        for a in actors:
-            ops = []
-            for _ in range(ops_per_file):
-                w = rng.choice(widths)
-                lo, hi = lim[w]
-                if ctr[a] and rng.random() < p_rm:
-                    ops.append(("Rm", C.VClock({a: rng.randint(1, ctr[a])}), [rng.randrange(members)]))
-                else:
-                    ctr[a] = max(ctr[a] + 1, rng.randint(lo, hi))
-                    mem = rng.randrange(members) if rng.random() < 0.5 else rng.randint(*lim[rng.choice(widths)])
-                    ops.append(("Add", (a, ctr[a]), [mem]))
-            files[a].append(ops)
-    return files
 
 
 @pytest.mark.parametrize("case", ["canonical", "well_formed", "adversarial", "large_files", "spurious_magic",

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import crdtenc
+from wave_run_corpus import OPEN_KEYS, _tail_length_batch
 
 pytestmark = pytest.mark.gpu
 H = bytes.fromhex
@@ -522,8 +523,10 @@ def test_reference_compact_format_is_unreadable_by_read_remote(ctx, tmp_path):
 
 @pytest.mark.parametrize("fused,fpw", [("1", "1"), ("1", "2"), ("1", "4"), ("2", "2"), ("2", "4")])
 def test_fused_geometries_match_oracle(ctx, oracle, fused, fpw, monkeypatch):
-    """k_open_fold_small (CE_FUSED=1) with 1, 2 and 4 files per wavefront and k_open_fold_v2
-    (CE_FUSED=2) with 2 and 4; mixed single-page sizes."""
+    """k_open_fold_small<64|32|16> (CE_FUSED=1 with 1, 2 and 4 files per wavefront),
+    k_open_fold_v2<32, 3, false, 3> (CE_FUSED=2 with 2) and the default k_open_fold_v3<false, true>
+    (CE_FUSED=2 with 4; k_open_fold_v2<16, ...> is reached only under CE_FUSED_V2, see
+    test_gpu_wave_runs.py); mixed single-page sizes.  The path counters say which kernel ran."""
     monkeypatch.setenv("CE_FILES_PER_WAVE", fpw)
     monkeypatch.setenv("CE_FUSED", fused)
     key = os.urandom(32)
@@ -547,6 +550,7 @@ def test_fused_geometries_match_oracle(ctx, oracle, fused, fpw, monkeypatch):
     orc, ost = oc.read_remote_ops(key, [APP], files, [actors[i] for i in fa], vers)
     assert rc == orc == 0 and st == ost
     assert core.state_bytes() == oc.serialize()
+    _only_open_kernel(core, fused, fpw)
     # one tampered file in the middle of a 4-file wave group: whole batch rejected
     bad = bytearray(files[50])
     bad[-20] ^= 8
@@ -556,36 +560,29 @@ def test_fused_geometries_match_oracle(ctx, oracle, fused, fpw, monkeypatch):
     empty = core2.state_bytes()
     rc, st = core2.ingest_ops(files2, actors, fa, vers)
     assert rc == 9 and st[50] == 9 and core2.state_bytes() == empty
+    _only_open_kernel(core2, fused, fpw)
 
 
-def _tail_length_batch(rng, actors, lens):
-    """Plaintexts of exactly the given lengths: APP || msgpack(Vec<Dot>) || trailing bytes
-    (rmp_serde::from_slice reads one value; the oracle ignores the tail the same way)."""
-    clears, fa, vers = [], [], []
-    per = -(-len(lens) // len(actors))
-    for i, L in enumerate(lens):
-        a, v = i // per, i % per
-        dots, body = [], msgpack.packb([])
-        while True:
-            d = {"actor": actors[a] if rng.random() < 0.8 else rng.choice(actors),
-                 "counter": rng.getrandbits(rng.choice([6, 16, 31, 40]))}
-            nb = msgpack.packb(dots + [d], use_bin_type=True)
-            if 16 + len(nb) > L:
-                break
-            dots.append(d)
-            body = nb
-        clears.append(APP + body + rng.randbytes(L - 16 - len(body)))
-        fa.append(a)
-        vers.append(v)
-    return clears, fa, vers
+FUSED_KERNEL_KEY = {("1", "1"): "open_small_lpf64", ("1", "2"): "open_small_lpf32", ("1", "4"): "open_small_lpf16",
+                    ("2", "2"): "open_v2_lpf32", ("2", "4"): "open_v3_p0e1"}
+
+
+def _only_open_kernel(core, fused, fpw):
+    """The open kernel these parameters reach today ran, and no other"""
+    key = FUSED_KERNEL_KEY[(fused, fpw)]
+    counts = {k: core.path_count(k) for k in OPEN_KEYS}
+    assert counts[key] >= 1 and all(v == 0 for k, v in counts.items() if k != key), counts
 
 
 @pytest.mark.parametrize("fused,fpw", [("1", "4"), ("2", "4"), ("2", "2")])
 def test_fused_every_tail_length(ctx, oracle, fused, fpw, monkeypatch):
     """Single-page files of every length class: each ciphertext length mod 64 (0..3 Poly1305
     pieces missing from the last ChaCha20 block, partial last pieces), the shortest envelopes and
-    the last 128 lengths up to one page, through both fused kernels; then tampered tags and
-    ciphertext bytes at several tail classes (per-file statuses == oracle, batch rejected)."""
+    the last 128 lengths up to one page, through k_open_fold_small<16> (CE_FUSED=1),
+    k_open_fold_v2<32, 3, false, 3> (CE_FUSED=2 with 2 files per wavefront) and the default
+    k_open_fold_v3<false, true> (CE_FUSED=2 with 4), as the path counters confirm; then tampered
+    tags and ciphertext bytes at several tail classes (per-file statuses == oracle, batch
+    rejected)."""
     monkeypatch.setenv("CE_FILES_PER_WAVE", fpw)
     monkeypatch.setenv("CE_FUSED", fused)
     key = os.urandom(32)
@@ -604,6 +601,7 @@ def test_fused_every_tail_length(ctx, oracle, fused, fpw, monkeypatch):
     orc, ost = oc.read_remote_ops(key, [APP], files, [actors[i] for i in fa], vers)
     assert rc == orc == 0 and st == ost
     assert core.state_bytes() == oc.serialize()
+    _only_open_kernel(core, fused, fpw)
     # tamper: the tag of one file per (length mod 64) class in 1..4 pieces-missing shapes, and a
     # ciphertext byte in the partial last piece of another
     bad = list(files)
@@ -628,6 +626,7 @@ def test_fused_every_tail_length(ctx, oracle, fused, fpw, monkeypatch):
     assert rc2 == orc2 == 9 and st2 == ost2
     assert all(st2[i] == 9 for i in picked.values())
     assert core2.state_bytes() == empty
+    _only_open_kernel(core2, fused, fpw)
 
 
 def test_unordered_batch_uses_host_gate(ctx, oracle):
