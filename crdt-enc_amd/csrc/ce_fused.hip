@@ -201,8 +201,17 @@ struct SupVers {
     v1 = a.n_supported > 1 ? *reinterpret_cast<const uint4*>(a.supported + 16) : make_uint4(0, 0, 0, 0);
   }
   __device__ __forceinline__ bool has(const DecodeArgs& a, const uint4& dv) const {
-    auto eq = [&](const uint4& x) { return dv.x == x.x && dv.y == x.y && dv.z == x.z && dv.w == x.w; };
-    bool found = (a.n_supported > 0 && eq(v0)) || (a.n_supported > 1 && eq(v1));
+    // whole-vector compares without short circuits: one LDS read of dv and four word ops (word
+    // by word, each compare was its own LDS read behind a branch).  v_bitop3 (a ^ b) | c keeps
+    // the compiler from turning the OR of XORs back into four compares.
+    auto eq = [&](const uint4& x) {
+      uint32_t d = dv.x ^ x.x;
+      d = __builtin_amdgcn_bitop3_b32(dv.y, x.y, d, 0xbe);
+      d = __builtin_amdgcn_bitop3_b32(dv.z, x.z, d, 0xbe);
+      d = __builtin_amdgcn_bitop3_b32(dv.w, x.w, d, 0xbe);
+      return d == 0;
+    };
+    bool found = ((uint32_t)(a.n_supported > 0) & (uint32_t)eq(v0)) | ((uint32_t)(a.n_supported > 1) & (uint32_t)eq(v1));
     for (uint32_t s = 2; s < a.n_supported; s++) found |= eq(*reinterpret_cast<const uint4*>(a.supported + 16 * s));
     return found;
   }
@@ -331,75 +340,96 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
           diff |= __builtin_amdgcn_alignbyte(e0[q + 1], e0[q], p0) ^ __builtin_amdgcn_alignbyte(e1[q + 1], e1[q], p1);
         tp = diff == 0;
       }
-      if (tp) {  // Dot 0 in full (every lane of the group; its actor is the file's)
-        const uint32_t* d = b32 + (pos >> 2);
-        uint32_t dd[13], w[12];
-#pragma unroll
-        for (int q = 0; q < 13; q++) dd[q] = d[q];
-#pragma unroll
-        for (int q = 0; q < 12; q++) w[q] = __builtin_amdgcn_alignbyte(dd[q + 1], dd[q], pos);
-        unsigned long long c0;
-        tp = canon_dot(w, L0, a0, a1, a2, a3, c0);
-      }
       if (__any(tp)) {
-        // the next file's parameters: issued once the template path is taken (it lands under the
-        // checks below; the per-Dot path issues it after its first round, whose actor-table
-        // loads would otherwise wait for it -- vmcnt counts in order)
-        prefetch();
-        pf_done = true;
-        // this lane's Dots k = sub + LPF j all start at byte shift s (LPF L0 = 0 mod 4): Dot 0's
-        // prefix laid out at that shift, E[q] = bytes 4q - s .. 4q - s + 3 of Dot 0, with the bytes
-        // outside the prefix masked in the first and last words (M0, M8, M9)
-        const uint32_t s = (pos + sub * L0) & 3u;
-        const int32_t ws = (int32_t)pos - (int32_t)s;  // >= -3: inside the file's LDS region
-        const uint32_t* A = reinterpret_cast<const uint32_t*>(body + (ws & ~3));
-        const uint32_t t = (uint32_t)ws & 3u;
-        uint32_t E[10];
+        // Dot 0 in full (its actor is the file's).  The window is read by every lane of the wave
+        // -- a lane off the template path reads its own region at pos, a few bytes in, and its
+        // result is dropped -- so the words stay in registers for the per-lane layout below
+        // instead of being read from LDS and aligned a second time.
+        uint32_t w[12];
         {
-          uint32_t Aw[11];
+          const uint32_t* d = b32 + (pos >> 2);
+          uint32_t dd[13];
 #pragma unroll
-          for (int q = 0; q < 11; q++) Aw[q] = tp ? A[q] : 0u;
+          for (int q = 0; q < 13; q++) dd[q] = d[q];
 #pragma unroll
-          for (int q = 0; q < 10; q++) E[q] = __builtin_amdgcn_alignbyte(Aw[q + 1], Aw[q], t);
+          for (int q = 0; q < 12; q++) w[q] = __builtin_amdgcn_alignbyte(dd[q + 1], dd[q], pos);
         }
-        const uint32_t M0 = ~0u << (8u * s);
-        const uint32_t M8 = s >= 2 ? ~0u : (s == 1 ? 0xffffffu : 0xffffu);
-        const uint32_t M9 = s == 3 ? 0xffu : 0u;
-        const uint32_t cw = L0 - 34u;                       // counter bytes: 1, 2, 4 or 8
-        const uint32_t csh = cw < 4 ? 32u - 8u * cw : 0u;
-        const uint32_t cnt = tp ? (uint32_t)remaining : 0u;
-        uint32_t bad = 0, mx = 0;
-        unsigned long long mx64 = 0;
-        for (uint32_t j = 0;; j++) {
-          const uint32_t k = sub + LPF * j;
-          const bool in = tp && k < cnt;
-          if (!__any(in)) break;
-          if (in) {
-            const uint32_t c = pos + k * L0;
-            const uint32_t* D = b32 + (c >> 2);
-            const uint32_t* Cc = b32 + ((c + 34u) >> 2);
-            uint32_t x = __builtin_amdgcn_bitop3_b32(D[0], E[0], M0, 0x28);  // (D ^ E) & M
-            x |= (D[1] ^ E[1]) | (D[2] ^ E[2]) | (D[3] ^ E[3]) | (D[4] ^ E[4]);
-            x |= (D[5] ^ E[5]) | (D[6] ^ E[6]) | (D[7] ^ E[7]);
-            x |= __builtin_amdgcn_bitop3_b32(D[8], E[8], M8, 0x28) | __builtin_amdgcn_bitop3_b32(D[9], E[9], M9, 0x28);
-            bad |= x;
-            const uint32_t u = c + 34u;  // counter bytes at shift (c + 34) mod 4
-            const uint32_t hi = bswap32(__builtin_amdgcn_alignbyte(Cc[1], Cc[0], u));
-            if (cw == 8) {
-              const uint32_t lo = bswap32(__builtin_amdgcn_alignbyte(Cc[2], Cc[1], u));
-              const unsigned long long v = ((unsigned long long)hi << 32) | lo;
-              mx64 = v > mx64 ? v : mx64;
-            } else {
-              const uint32_t v = hi >> csh;
-              mx = v > mx ? v : mx;
+        unsigned long long c0;
+        tp = ((uint32_t)tp & (uint32_t)canon_dot(w, L0, a0, a1, a2, a3, c0)) != 0;
+        if (__any(tp)) {
+          // this lane's Dots k = sub + LPF j all start at byte shift s (LPF L0 = 0 mod 4): Dot 0's
+          // prefix laid out at that shift, E[q] = bytes 4q - s .. 4q - s + 3 of Dot 0, with the bytes
+          // outside the prefix masked in the first and last words (M0, M8, M9).  E[q] is bytes
+          // 4 - s .. 7 - s of the pair (w[q - 1], w[q]): one v_perm each, its selector per lane.
+          // (E[0]'s bytes before Dot 0 and E[9]'s past w[8] are masked, so zeros stand in there.)
+          const uint32_t s = (pos + sub * L0) & 3u;
+          const uint32_t esel = 0x07060504u - 0x01010101u * s;
+          uint32_t E[10];
+#pragma unroll
+          for (int q = 0; q < 10; q++)
+            E[q] = __builtin_amdgcn_perm(q < 9 ? w[q] : 0u, q > 0 ? w[q - 1] : 0u, esel);
+          // the next file's parameters: issued once the template path is taken and Dot 0's window
+          // is consumed (it lands under the checks below; the per-Dot path issues it after its
+          // first round, whose actor-table loads would otherwise wait for it -- vmcnt counts in
+          // order)
+          prefetch();
+          pf_done = true;
+          const uint32_t M0 = ~0u << (8u * s);
+          const uint32_t M8 = s >= 2 ? ~0u : (s == 1 ? 0xffffffu : 0xffffu);
+          const uint32_t M9 = s == 3 ? 0xffu : 0u;
+          const uint32_t cw = L0 - 34u;                       // counter bytes: 1, 2, 4 or 8
+          const uint32_t csh = cw < 4 ? 32u - 8u * cw : 0u;
+          const uint32_t cnt = tp ? (uint32_t)remaining : 0u;
+          uint32_t lim = cnt;  // the loop's bound: 0 once the group is off the path, so that "in"
+                               // is one compare (a vote on tp && k < cnt costs two more per trip)
+          // the counter's first four bytes sit at byte s + 2 of the words D[8..10] (34 = 32 + 2):
+          // big-endian bytes s .. s + 3 of D[8..10] >> 16, reversed by the same v_perm
+          const uint32_t csel = 0x00010203u + 0x01010101u * s;
+          uint32_t bad = 0, mx = 0;
+          unsigned long long mx64 = 0;
+          for (uint32_t j = 0;; j++) {
+            const uint32_t k = sub + LPF * j;
+            const bool in = k < lim;
+            if (!__any(in)) break;
+            if (in) {
+              const uint32_t c = pos + k * L0;
+              const uint32_t* D = b32 + (c >> 2);
+              // bad |= (D ^ E) [& M] over the ten words, as two chains of (D ^ E) | x
+              uint32_t x = __builtin_amdgcn_bitop3_b32(D[0], E[0], M0, 0x28);  // (D ^ E) & M
+              uint32_t y = __builtin_amdgcn_bitop3_b32(D[8], E[8], M8, 0x28);
+              const uint32_t z = __builtin_amdgcn_bitop3_b32(D[9], E[9], M9, 0x28);
+              x = __builtin_amdgcn_bitop3_b32(D[1], E[1], x, 0xbe);  // (D ^ E) | x
+              y = __builtin_amdgcn_bitop3_b32(D[2], E[2], y, 0xbe);
+              x = __builtin_amdgcn_bitop3_b32(D[3], E[3], x, 0xbe);
+              y = __builtin_amdgcn_bitop3_b32(D[4], E[4], y, 0xbe);
+              x = __builtin_amdgcn_bitop3_b32(D[5], E[5], x, 0xbe);
+              y = __builtin_amdgcn_bitop3_b32(D[6], E[6], y, 0xbe);
+              x = __builtin_amdgcn_bitop3_b32(D[7], E[7], x, 0xbe);
+              bad |= x | y | z;
+              const uint32_t c89 = __builtin_amdgcn_alignbyte(D[9], D[8], 2);
+              const uint32_t c9a = __builtin_amdgcn_alignbyte(D[10], D[9], 2);
+              const uint32_t hi = __builtin_amdgcn_perm(c9a, c89, csel);
+              if (cw == 8) {
+                const uint32_t u = c + 34u;  // counter bytes at shift (c + 34) mod 4
+                const uint32_t* Cc = b32 + (u >> 2);
+                const uint32_t lo = bswap32(__builtin_amdgcn_alignbyte(Cc[2], Cc[1], u));
+                const unsigned long long v = ((unsigned long long)hi << 32) | lo;
+                mx64 = v > mx64 ? v : mx64;
+              } else {
+                const uint32_t v = hi >> csh;
+                mx = v > mx ? v : mx;
+              }
+            }
+            if (j == 0 && grp_bits<LPF>(bad != 0, grp)) {  // another actor: stop early
+              tp = false;
+              lim = 0;
             }
           }
-          if (j == 0 && grp_bits<LPF>(bad != 0, grp)) tp = false;  // another actor: stop early
-        }
-        if (grp_bits<LPF>(bad != 0, grp)) tp = false;
-        if (tp) {
-          if (do_fold && sub < cnt) fold_dot(a0, a1, a2, a3, cw == 8 ? mx64 : (unsigned long long)mx);
-          remaining = 0;
+          if (grp_bits<LPF>(bad != 0, grp)) tp = false;
+          if (tp) {
+            if (do_fold && sub < cnt) fold_dot(a0, a1, a2, a3, cw == 8 ? mx64 : (unsigned long long)mx);
+            remaining = 0;
+          }
         }
       }
     }
