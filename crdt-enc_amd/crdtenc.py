@@ -12,7 +12,7 @@ import ctypes
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# CRDTENC_LIB selects another in-tree build (e.g. libcrdtenc_prof.so, the diagnostics build)
+# CRDTENC_LIB selects another build of the library (e.g. an earlier commit's, for a same-box A/B)
 LIB_PATH = os.environ.get("CRDTENC_LIB") or os.path.join(HERE, "libcrdtenc.so")
 
 OK = 0

@@ -889,18 +889,6 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
   da.nil_actor = table_has_nil(c);
   da.batch = c->d_batch.as<unsigned long long>();
   da.large_list = ctx->large.as<uint32_t>();
-#if CE_FUSED_DIAG  // diagnostics build (make prof -> libcrdtenc_prof.so)
-  if (const char* ab = getenv("CE_ABLATE")) da.ablate = atoi(ab);
-  const bool prof = getenv("CE_PROF") != nullptr;
-#else
-  const bool prof = false;
-#endif
-  static DevBuf& prof_buf = *new DevBuf;  // CE_PROF diagnostics (never freed): per-wave phase cycles
-  if (prof) {
-    if ((e = prof_buf.reserve(8ull * 8 * 65536)) || (e = hipMemsetAsync(prof_buf.p, 0, 8ull * 8 * 65536, ctx->stream)))
-      return ctx->hip_fail(e, "prof");
-    da.prof = prof_buf.as<unsigned long long>();
-  }
 
   // 2) GPU: single-page files: open + decode + fold fused; larger files: segments + decode
   ctx->open_log.grid_cap = test_grid_cap();
@@ -1020,26 +1008,6 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
   if (!host_tail &&
       (e = hipMemcpyAsync(hnov, gbase + 16ull * m, m * 8ull, hipMemcpyDeviceToHost, ctx->stream)))
     return ctx->hip_fail(e, "nov");
-  if (prof) {
-    std::vector<unsigned long long> hp(8ull * 65536);
-    if ((e = hipMemcpyAsync(hp.data(), prof_buf.p, hp.size() * 8, hipMemcpyDeviceToHost, ctx->stream)) ||
-        (e = stream_wait(ctx->stream)))
-      return ctx->hip_fail(e, "prof");
-    double sum[7] = {0, 0, 0, 0, 0, 0, 0};
-    uint32_t waves = 0;
-    for (size_t w = 0; w < 65536; w++)
-      if (hp[8 * w + 6]) {
-        waves++;
-        for (int i = 0; i < 7; i++) sum[i] += (double)hp[8 * w + i];
-      }
-    if (waves)
-      // phase order: k_open_fold_small = params, chacha, xor_horner, tree_tag, decode prelude,
-      // decode rounds; k_open_fold_v2 = setup, first block, middle blocks, last block,
-      // tree_tag, decode
-      fprintf(stderr, "CE_PROF waves %u iters/wave %.1f cycles/iter: p0 %.0f p1 %.0f p2 %.0f "
-              "p3 %.0f p4 %.0f p5 %.0f\n", waves, sum[6] / waves,
-              sum[0] / sum[6], sum[1] / sum[6], sum[2] / sum[6], sum[3] / sum[6], sum[4] / sum[6], sum[5] / sum[6]);
-  }
   uint32_t* hc = ctx->h_counters.as<uint32_t>();
   if ((!host_tail && (e = hipMemcpyAsync(hc, ctx->counters.p, 64, hipMemcpyDeviceToHost, ctx->stream))) ||
       (e = ctx->sync_spin()))

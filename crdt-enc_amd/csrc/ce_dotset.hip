@@ -1901,7 +1901,7 @@ struct MaxOp {
 };
 }  // namespace
 
-// the stable pair sorts: the hand-written LSD radix sort of ce_ser_sort.hip (no hipCUB)
+// the stable pair sorts: the hand-written LSD radix sort of ce_ser_sort.hip
 hipError_t ds_sort_pairs_u32(void* tmp, size_t& tb, const uint32_t* kin, uint32_t* kout,
                              const uint32_t* vin, uint32_t* vout, uint32_t n, int bits, hipStream_t s) {
   return sort_pairs_u32(tmp, tb, kin, kout, vin, vout, n, bits, s);
@@ -1913,7 +1913,7 @@ hipError_t ds_sort_pairs_u64(void* tmp, size_t& tb, const unsigned long long* ki
   return sort_pairs_u64(tmp, tb, kin, kout, vin, vout, n, 64, s);
 }
 
-// ds_excl_max_by_key / ds_excl_sum_u32: ce_scan.hip (no hipCUB: its scans query the device
+// ds_excl_max_by_key / ds_excl_sum_u32: ce_scan.hip (rocPRIM's look-back scans query the device
 // properties on the host at every call)
 
 // One block after the count pass and its scan, so the host reads everything the emit's sizing

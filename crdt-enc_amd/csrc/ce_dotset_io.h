@@ -94,7 +94,7 @@ inline size_t ser_sort_state_words(uint32_t n) {
 // kbuf: two key buffers of n (u32 when key_bits <= 32, else u64), vbuf: two u64 buffers of n
 hipError_t launch_ser_sort(hipStream_t s, const SerSortArgs& a, void* const kbuf[2], unsigned long long* const vbuf[2]);
 // Stable LSD radix sort of (key, u32 value) pairs over the key's low `bits` bits (the same
-// kernels as the serializer's sort; hipCUB's DeviceRadixSort::SortPairs interface: tmp == null ->
+// kernels as the serializer's sort; rocPRIM-style two-call interface: tmp == null ->
 // *tb = the scratch bytes needed).  kin / vin are not modified; kout / vout may not alias them.
 hipError_t sort_pairs_u32(void* tmp, size_t& tb, const uint32_t* kin, uint32_t* kout, const uint32_t* vin,
                           uint32_t* vout, uint32_t n, int bits, hipStream_t s);

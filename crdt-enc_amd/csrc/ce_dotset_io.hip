@@ -19,9 +19,6 @@
 #include <cstdlib>
 
 #include <algorithm>
-#if CE_FUSED_DIAG  // hipCUB only for the diagnostics build's A/B (CE_SER_CUB)
-#include <hipcub/hipcub.hpp>
-#endif
 #include <map>
 #include <mutex>
 
@@ -84,27 +81,6 @@ __global__ void k_ser_gather2(const uint32_t* perm, const uint32_t* actor_in, co
 __global__ void k_ser_gather_member(const uint32_t* perm, const unsigned long long* member_in,
                                     unsigned long long* member_out, uint32_t n) {
   for (uint32_t i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB) member_out[i] = member_in[perm[i]];
-}
-
-// one sort when (member, rank) packs into K: key = member << rank_bits | rank ((member, actor)
-// pairs are unique, so no two keys tie); the values ride through the sort itself
-template <typename K>
-__global__ void k_ser_key(const uint32_t* actor, const uint32_t* rank_of_id, const unsigned long long* member,
-                          int rank_bits, K* key, uint32_t n) {
-  for (uint32_t i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB)
-    key[i] = ((K)member[i] << rank_bits) | (K)rank_of_id[actor[i]];
-}
-
-// member and actor id back out of the sorted key (member_out may alias key): no gather
-template <typename K>
-__global__ void k_ser_unpack(const K* key, int rank_bits, const uint32_t* id_of_rank, unsigned long long* member_out,
-                             uint32_t* actor_out, uint32_t n) {
-  const K mask = ((K)1 << rank_bits) - 1;
-  for (uint32_t i = blockIdx.x * kB + threadIdx.x; i < n; i += gridDim.x * kB) {
-    const K k = key[i];
-    actor_out[i] = id_of_rank[(uint32_t)(k & mask)];
-    member_out[i] = (unsigned long long)(k >> rank_bits);
-  }
 }
 
 // head[i] = pair i starts a member's entry
@@ -789,18 +765,13 @@ hipError_t launch_orswot_ser(hipStream_t s, OrswotSerScratch& sc, const OrswotSe
 
 hipError_t launch_orswot_ser_sort(hipStream_t s, OrswotSerScratch& sc, uint32_t n) {
   // pairs (member, actor id, value) in collect order -> sorted by (member, rank): the hand-written
-  // radix sort of the packed (member, rank) key when it fits 64 bits (ce_ser_sort.hip; CE_SER_CUB=1:
-  // hipCUB's sort of the same key, for A/B), else (or CE_SER_TWO_SORTS=1) the general form -- sort
-  // by rank, then stably by member, LSD order -- and a gather
+  // radix sort of the packed (member, rank) key when it fits 64 bits (ce_ser_sort.hip), else (or
+  // CE_SER_TWO_SORTS=1) the general form -- sort by rank, then stably by member, LSD order -- and
+  // a gather
   hipError_t e;
   const int kb = sc.member_bits + sc.rank_bits;
-#if CE_FUSED_DIAG
-  static const bool cub = getenv("CE_SER_CUB") != nullptr;  // diagnostics build: hipCUB's sort, A/B
-#else
-  constexpr bool cub = false;
-#endif
   const bool two = getenv("CE_SER_TWO_SORTS") != nullptr;  // (the tests flip it)
-  if (n && kb <= 64 && !two && !cub && n < (1u << 30)) {
+  if (n && kb <= 64 && !two && n < (1u << 30)) {
     SerSortArgs a{};
     a.member_in = sc.member_in;
     a.actor_in = sc.actor_in;
@@ -820,28 +791,6 @@ hipError_t launch_orswot_ser_sort(hipStream_t s, OrswotSerScratch& sc, uint32_t 
     void* kbuf[2] = {kb <= 32 ? (void*)sc.k32a : (void*)sc.k64a, kb <= 32 ? (void*)sc.k32b : (void*)sc.k64b};
     unsigned long long* vbuf[2] = {sc.v64a, sc.v64b};
     if ((e = launch_ser_sort(s, a, kbuf, vbuf))) return e;
-#if CE_FUSED_DIAG
-  } else if (n && kb <= 64 && !two) {
-    // (member, rank) in one key: hipCUB's radix sort over member_bits + rank_bits
-    size_t tb = sc.tmp_bytes;
-    if (kb <= 32) {
-      hipLaunchKernelGGL(k_ser_key<uint32_t>, dim3(nblk(n)), dim3(kB), 0, s, sc.actor_in, sc.rank_of_id, sc.member_in,
-                         sc.rank_bits, sc.k32a, n);
-      if ((e = hipcub::DeviceRadixSort::SortPairs(sc.tmp, tb, sc.k32a, sc.k32b, sc.value_in, sc.value_sorted, (int)n,
-                                                   0, kb, s)))
-        return e;
-      hipLaunchKernelGGL(k_ser_unpack<uint32_t>, dim3(nblk(n)), dim3(kB), 0, s, sc.k32b, sc.rank_bits, sc.id_of_rank,
-                         sc.member_sorted, sc.actor_sorted, n);
-    } else {
-      hipLaunchKernelGGL(k_ser_key<unsigned long long>, dim3(nblk(n)), dim3(kB), 0, s, sc.actor_in, sc.rank_of_id,
-                         sc.member_in, sc.rank_bits, sc.k64a, n);
-      if ((e = hipcub::DeviceRadixSort::SortPairs(sc.tmp, tb, sc.k64a, sc.member_sorted, sc.value_in, sc.value_sorted,
-                                                   (int)n, 0, kb, s)))
-        return e;
-      hipLaunchKernelGGL(k_ser_unpack<unsigned long long>, dim3(nblk(n)), dim3(kB), 0, s, sc.member_sorted,
-                         sc.rank_bits, sc.id_of_rank, sc.member_sorted, sc.actor_sorted, n);
-    }
-#endif
   } else if (n) {
     // the general form (keys past 64 bits, CE_SER_TWO_SORTS): two stable pair sorts of the
     // hand-written radix sort (ce_ser_sort.hip), by rank, then by member
@@ -917,14 +866,7 @@ static size_t ser_tmp_bytes_raw(uint32_t n) {
   (void)sort_pairs_u32(nullptr, a, nullptr, nullptr, nullptr, nullptr, n, 32, nullptr);
   (void)sort_pairs_u64(nullptr, b, nullptr, nullptr, nullptr, nullptr, n, 64, nullptr);
   (void)ds_excl_sum_u32(nullptr, c, nullptr, nullptr, n, nullptr);
-  size_t d = 0, e = 0;
-#if CE_FUSED_DIAG  // CE_SER_CUB: the packed-key sorts through hipCUB, u64 values
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, d, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                           (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)n, 0, 32);
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, e, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                           (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)n, 0, 64);
-#endif
-  return std::max(std::max(a, b), std::max(c, std::max(d, e))) + 256;
+  return std::max(std::max(a, b), c) + 256;
 }
 
 size_t orswot_ser_tmp_bytes(uint32_t n) {

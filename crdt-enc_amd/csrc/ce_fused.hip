@@ -220,35 +220,15 @@ struct SupVers {
 // `prefetch` (the next file's parameters) is called once, after the decode's first round: a
 // global load issued before the round's actor-table lookups would be waited for with them
 // (vmcnt counts in order), exposing its latency.
-// DOPT (diagnostics of k_open_fold_v2's OPT 128 / 256 / 512 / 1024, results invalid for 128):
-// 1 = actor lookups replaced by the hash slot (no table load), 2 = the flush's atomicMax without
-// its read, 4 = one extra ChaCha20 block's double rounds spread over the fast rounds (one per
-// round, the rest after the loop), 8 = the same extra block after the decode loops (4 vs 8:
-// how much independent VALU work the decode's stalls could absorb)
 // PN: the op grammar is Vec<pncounter::Op<Uuid>> (canon_pn_op / parse_pn_op) and a.batch holds two
 // planes, Pos at [slot] and Neg at [slot + mask + 1]; the fold index carries the plane, so the
 // pending (index, max), its carry and the flush are the Dot form's.  Every PN difference is an
 // `if constexpr`: the Dot instantiations compile the code they always did.
-template <int LPF, int DOPT = 0, bool CARRY = false, bool PN = false, typename Pf>
+template <int LPF, bool CARRY = false, bool PN = false, typename Pf>
 __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& sup, const uint8_t* fl,
                                             uint32_t len, bool live, bool apply, uint32_t f,
                                             uint32_t grp, uint32_t sub, DecState& S, Pf&& prefetch) {
-#if !CE_FUSED_DIAG
-  static_assert(DOPT == 0, "decode_fold diagnostics variants exist only in the diagnostics build");
-#endif
   int32_t st = CE_OK;
-  uint32_t xs[16];
-  int drn = 0;
-  auto dround = [&] {
-    CE_QR_T(true, xs[0], xs[4], xs[8], xs[12]); CE_QR_T(true, xs[1], xs[5], xs[9], xs[13]);
-    CE_QR_T(true, xs[2], xs[6], xs[10], xs[14]); CE_QR_T(true, xs[3], xs[7], xs[11], xs[15]);
-    CE_QR_T(true, xs[0], xs[5], xs[10], xs[15]); CE_QR_T(true, xs[1], xs[6], xs[11], xs[12]);
-    CE_QR_T(true, xs[2], xs[7], xs[8], xs[13]); CE_QR_T(true, xs[3], xs[4], xs[9], xs[14]);
-  };
-  if (DOPT & 12) {
-#pragma unroll
-    for (int i = 0; i < 16; i++) xs[i] = f * 16u + (uint32_t)i + sub;
-  }
   if (live) {
     if (len < 16) st = CE_ERR_PT_LEN;
     else if (!sup.has(a, *reinterpret_cast<const uint4*>(fl))) st = CE_ERR_PT_VERSION;
@@ -294,10 +274,7 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
                       uint32_t dir = 0) {
     uint32_t slot;
     if (cached(k0, k1, k2, k3)) slot = S.cslot;
-    else if (DOPT & 1) {
-      slot = actor_hash(k0, k1, k2, k3) & a.mask;
-      remember(slot, k0, k1, k2, k3);
-    } else {
+    else {
       slot = lookup_slot1(a.table, a.mask, a.nil_actor, k0, k1, k2, k3);
       remember(slot, k0, k1, k2, k3);
     }
@@ -511,10 +488,6 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
 #pragma unroll
         for (int q = 0; q < 13; q++) dd[h][q] = d[q];
       }
-      if ((DOPT & 4) && drn < 10) {
-        dround();
-        drn++;
-      }
 #pragma unroll
       for (int h = 0; h < 2; h++) {
         const uint32_t sh = cand[h] & 3;
@@ -543,10 +516,6 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
     }
     pos += done * L0;
     remaining -= done;
-  }
-  if (DOPT & 12) {
-#pragma unroll 1
-    for (; drn < 10; drn++) dround();
   }
   if (!pf_done) {
     prefetch();
@@ -649,19 +618,12 @@ __device__ __forceinline__ void decode_fold(const DecodeArgs& a, const SupVers& 
     const uint32_t mx = grp_reduce<LPF>(hi, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
     const uint32_t mn = grp_reduce<LPF>(lo, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
     const unsigned long long b = grp_max64<LPF>(pslot == 0xffffffffu ? 0ull : pbest);
-#if CE_FUSED_DIAG
-    if (a.ablate & 16) {  // diagnostics: no fold atomics (results invalid)
-    } else
-#endif
     if (mx != 0 && mn == mx) {
-      if (DOPT & 2) {
-        if (sub == 0) atomicMax(&a.batch[mx - 1], b);
-      } else if (sub == 0) batch_max(&a.batch[mx - 1], b);
+      if (sub == 0) batch_max(&a.batch[mx - 1], b);
     } else if (pslot != 0xffffffffu) {
       batch_max(&a.batch[pslot], pbest);
     }
   }
-  if ((DOPT & 12) && (xs[0] ^ xs[5] ^ xs[10] ^ xs[15]) == 0x9e3779b9u) a.status[f] = 77;
   if (live && st != CE_OK && sub == 0) {
     a.status[f] = st;
     atomicAdd(&a.counters[3], 1u);
@@ -682,20 +644,6 @@ void k_open_fold_small(DecodeArgs a) {
   uint8_t* fl = lds + (wib * F + grp) * kRegion;
   const uint32_t ngroups = (a.n + F - 1) / F;
   const uint32_t stride = gridDim.x * C::WPB;
-  // CE_PROF: s_memtime at phase boundaries, summed per wave (params+loads, ChaCha20,
-  // XOR+Horner, tree+tag, decode prelude, decode rounds+flush, iterations)
-#if CE_FUSED_DIAG
-  unsigned long long pc[7] = {0, 0, 0, 0, 0, 0, 0};
-  unsigned long long tp = a.prof ? __builtin_amdgcn_s_memtime() : 0;
-#define CE_PHASE(i)                                            \
-  if (a.prof) {                                                \
-    const unsigned long long tn = __builtin_amdgcn_s_memtime(); \
-    pc[i] += tn - tp;                                          \
-    tp = tn;                                                   \
-  }
-#else
-#define CE_PHASE(i)
-#endif
 
   uint32_t g = bcast(blockIdx.x * C::WPB + wib);
   FilePre nx = load_pre<C::LOG + C::LOGCH>(a, g * F + grp);
@@ -729,12 +677,8 @@ void k_open_fold_small(DecodeArgs a) {
       // inside the file; bytes past len are zeroed below (Poly1305 pad16, plaintext tail).
       // Slots before the first piece load the file's first piece (in bounds), never used.
       ct[j] = *reinterpret_cast<const uint4*>(src + boff);
-#if CE_FUSED_DIAG
-      if (a.ablate & 8) ct[j] = make_uint4(boff, len, sub, 0);
-#endif
     }
     __builtin_amdgcn_wave_barrier();
-    CE_PHASE(0)
 
     // 2) keystream: lane computes blocks sub + LPF*k (ChaCha20 counter 1 + block); the
     //    counter-independent first-round work is shared by the lane's F blocks
@@ -744,13 +688,7 @@ void k_open_fold_small(DecodeArgs a) {
       const uint32_t b = sub + LPF * k;
       if (act && b * 64 < len) {
         uint32_t kb[16];
-#if CE_FUSED_DIAG
-        if (a.ablate & 4) {
-#pragma unroll
-          for (int i = 0; i < 16; i++) kb[i] = cur.key[i & 7] + b;
-        } else
-#endif
-          chacha_block_pre(cpre, cur.key, 1u + b, 0u, cur.n2a, cur.n2b, kb);
+        chacha_block_pre(cpre, cur.key, 1u + b, 0u, cur.n2a, cur.n2b, kb);
         uint4* kd = reinterpret_cast<uint4*>(fl + b * kKsStride);
         kd[0] = make_uint4(kb[0], kb[1], kb[2], kb[3]);
         kd[1] = make_uint4(kb[4], kb[5], kb[6], kb[7]);
@@ -759,7 +697,6 @@ void k_open_fold_small(DecodeArgs a) {
       }
     }
     __builtin_amdgcn_wave_barrier();
-    CE_PHASE(1)
 
     // tree powers r^(2^k), k < LOG + 2 (r^LPF, r^2LPF combine the chains), and s || expected
     // tag: 16-byte loads issued now, used after the Horner pass (their latency hides under it).
@@ -811,11 +748,7 @@ void k_open_fold_small(DecodeArgs a) {
         uint4 y = make_uint4(x.x ^ (k4.x & kw_mask[0]), x.y ^ (k4.y & kw_mask[1]),
                              x.z ^ (k4.z & kw_mask[2]), x.w ^ (k4.w & kw_mask[3]));
         *reinterpret_cast<uint4*>(fl + boff) = y;
-#if CE_FUSED_DIAG
-        if (a.ablate & 2) acc[c].v[j % 5] += x.x ^ x.w;
-        else
-#endif
-          acc[c] = add5(mulmod(acc[c], RS), block_limbs(x.x, x.y, x.z, x.w));
+        acc[c] = add5(mulmod(acc[c], RS), block_limbs(x.x, x.y, x.z, x.w));
       }
     }
     // lane value = sum_c acc_c * (r^LPF)^c
@@ -833,7 +766,6 @@ void k_open_fold_small(DecodeArgs a) {
       lv = carry5(lv);
     }
     __builtin_amdgcn_wave_barrier();
-    CE_PHASE(2)
 
     // 4) cross-lane tree inside the group: U = sum_s lane_s * r^s (level k adds lane s + 2^k
     //    times r^(2^k): DPP row shifts up to 8 lanes), then T = U * r.  Only position 0 (sub 0)
@@ -863,33 +795,15 @@ void k_open_fold_small(DecodeArgs a) {
       if (!tag_ok) a.status[f] = CE_ERR_AUTH;
     }
     fails.add(act && sub == 0 && !tag_ok, f);
-    bool ok = grp_bits<LPF>(tag_ok, grp) != 0;
+    const bool ok = grp_bits<LPF>(tag_ok, grp) != 0;
 
-    CE_PHASE(3)
-
-    // 5)+6) data-version check, decode from LDS, fold
-#if CE_FUSED_DIAG
-    if (a.ablate) ok = !(a.ablate & 1);
-#endif
-    CE_PHASE(4)
+    // 5)+6) data-version check, decode from LDS, fold;
     // the next iteration's parameters are loaded inside (their latency hides under the decode)
     decode_fold<LPF>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, S,
                      [&] { nx = load_pre<C::LOG + C::LOGCH>(a, (g + stride) * F + grp); });
     __builtin_amdgcn_wave_barrier();
-    CE_PHASE(5)
-#if CE_FUSED_DIAG
-    pc[6]++;
-#endif
   }
   fails.flush(a);
-#undef CE_PHASE
-#if CE_FUSED_DIAG
-  if (a.prof && lane == 0) {
-    unsigned long long* o = a.prof + 8ull * (blockIdx.x * C::WPB + wib);
-#pragma unroll
-    for (int i = 0; i < 7; i++) o[i] = pc[i];
-  }
-#endif
 }
 
 // Resident blocks per CU for a kernel, from the occupancy calculator (LDS and VGPRs both
@@ -961,7 +875,12 @@ struct FilePre2 {
   uint32_t n2a, n2b;
   uint32_t R1[5];   // r
   uint32_t R64[5];  // r^64
-  uint32_t R2[5];   // r^2 (used by OPT 64 only; dead loads otherwise)
+  // r^2: no kernel reads it from here (they load rpow[1] where they use it), yet dropping it is
+  // not free: compiled without the member, every k_open_fold_v3 form and the 4-files-per-wave
+  // k_open_fold_v2 come out 1 to 41 instructions shorter and k_open_fold_v3<false, false> one
+  // VGPR larger (rpow[1] follows rpow[0], R1, in memory).  So it goes with a measured change,
+  // not with a cleanup.
+  uint32_t R2[5];
 };
 
 __device__ __forceinline__ FilePre2 load_pre2(const DecodeArgs& a, uint32_t f) {
@@ -1260,36 +1179,26 @@ __device__ __forceinline__ bool ds_fused_decode(const DecodeArgs& a, const SupVe
 #define CE_DS_PRIO 2
 #endif
 // W = waves per SIMD the VGPR budget is sized for (LDS allows 2.5 at LPF 16, 5 at LPF 32).
-// OPT bits: 1 = rot16 as two SDWA xors (ce_device.h xor_rotl16_t), 2 = the next iteration's
-// ciphertext loads issued inside this iteration's decode (after its first round, with the
-// parameters loaded one iteration earlier), so they land while the decode and the next
-// iteration's first ChaCha20 block run instead of being waited for at the first XOR;
-// 4 / 8 = ChaCha20's 9 trailing double rounds as a rolled loop of 1 / 3 (instruction bytes);
-// 16 = one block of the next iteration's ciphertext in flight across the iteration boundary.
+// PF = the next iteration's ciphertext loads issued inside this iteration's decode (after its
+// first round, with the parameters loaded one iteration earlier), so they land while the decode
+// and the next iteration's first ChaCha20 block run instead of being waited for at the first
+// XOR.  On for the 2-files-per-wave form only (the measured defaults, same-box A/B r02).
+// ChaCha20's rot16 is two SDWA xors in every form (ce_device.h xor_rotl16_t<true>); its 9
+// trailing double rounds are straight-line in the decoding forms and a rolled loop of
+// CE_V2_OPEN_UNR per trip in the open-only and DS forms.
 // DEC = false: open only (EncHandler::decrypt, xchacha lib.rs:73-101) -- plaintext pieces go to
 // HBM at the file's out_off instead of LDS, the tag check sets the status, nothing is decoded
 // (the dot-set ingest decodes the plaintext afterwards).
 // DS (with DEC = false): Orswot op files of at most kDsFuseRegion bytes keep their plaintext in LDS
 // and are decoded there (ds_fused_decode); larger ones, and any the decode does not prove, get
 // their plaintext in HBM as in the open-only form.
-template <int LPF, int W, bool JIT, int OPT = 3, bool DEC = true, bool DS = false>
+template <int LPF, int W, bool PF, bool DEC = true, bool DS = false>
 __global__ __launch_bounds__(64, W)
 void k_open_fold_v2(DecodeArgs a) {
   static_assert(!(DEC && DS), "the DS form is an open-only form");
-#if !CE_FUSED_DIAG
-  static_assert((OPT & ~3) == 0, "k_open_fold_v2 diagnostics variants exist only in the diagnostics build");
-#endif
-  constexpr bool SD = (OPT & 1) != 0;
-  constexpr bool PF = (OPT & 2) != 0 && !JIT;
+  static_assert(DEC || !PF, "the prefetch is issued from inside the decode");
   // ChaCha20 double rounds per loop trip (the open-only and DS forms: CE_V2_OPEN_UNR)
-  constexpr int UNR = (OPT & 4) ? 1 : (OPT & 8) ? 3 : DEC ? 9 : CE_V2_OPEN_UNR;
-  // OPT 16: the first-processed block (k = BPL - 1) of the NEXT iteration is loaded as soon as
-  // this iteration has consumed its own (its parameters are loaded at this iteration's start)
-  constexpr bool PF1 = (OPT & 16) != 0 && !PF && !JIT;
-  // OPT 64: parameters two iterations ahead, loaded after the decode's last global read (its
-  // flush), with r^2 among them -- no wait inside an iteration covers a load issued in it
-  // before its own ciphertext
-  constexpr bool DP = (OPT & 64) != 0 && !PF;
+  constexpr int UNR = DEC ? 9 : CE_V2_OPEN_UNR;
   using C = V2Cfg<LPF>;
   constexpr int F = C::F;
   constexpr int BPL = C::BPL;
@@ -1326,36 +1235,9 @@ void k_open_fold_v2(DecodeArgs a) {
       const uint32_t q = (uint32_t)(4 * b + j);
       const uint32_t off = b >= 0 && q < npc_ ? q * 16u : 0u;
       ct[k][j] = *reinterpret_cast<const uint4*>(src_ + off);
-#if CE_FUSED_DIAG
-      if (a.ablate & 8) ct[k][j] = make_uint4(off, len_, sub, (uint32_t)k);
-#endif
     }
   };
   FilePre2 nn;  // PF: the parameters of the iteration after next
-  // CE_PROF (diagnostics build): s_memtime at phase boundaries, summed per wave: setup, first
-  // block (waits for its ciphertext), middle blocks, last block, tree+tag, decode, iterations
-#if CE_FUSED_DIAG
-  unsigned long long pc[7] = {0, 0, 0, 0, 0, 0, 0};
-  unsigned long long tp = a.prof ? __builtin_amdgcn_s_memtime() : 0;
-#define CE_PHASE2(i)                                           \
-  if (a.prof) {                                                \
-    const unsigned long long tn = __builtin_amdgcn_s_memtime(); \
-    pc[i] += tn - tp;                                          \
-    tp = tn;                                                   \
-  }
-#else
-#define CE_PHASE2(i)
-#endif
-  if (OPT & 32) {
-    // diagnostics: waves in odd SIMD slots start ~half an iteration late (phase-locked waves?)
-    const uint32_t hw = __builtin_amdgcn_s_getreg((3 << 11) | 4);  // HW_ID.WAVE_ID
-    if (hw & 1) {
-      __builtin_amdgcn_s_sleep(127);
-      __builtin_amdgcn_s_sleep(127);
-    }
-  }
-  if (PF1) load_block_of(nx, BPL - 1);
-  if (DP) nn = load_pre2(a, (g + stride) * F + grp);
   if (PF) {
     // prologue: this wave's first ciphertext, and the next iteration's parameters
 #pragma unroll
@@ -1366,8 +1248,7 @@ void k_open_fold_v2(DecodeArgs a) {
   for (; g < ngroups; g += stride) {
     const uint32_t f = g * F + grp;
     const FilePre2 cur = nx;
-    if (PF || DP) nx = nn;
-    if (PF1 && !DP) nx = load_pre2(a, (g + stride) * F + grp);  // issued before this iteration's loads
+    if (PF) nx = nn;
     if (DS && a.only && !__any(cur.ok)) {  // a masked pass (k_open_ds8's big files): nothing here
       nx = load_pre2(a, (g + stride) * F + grp);
       continue;
@@ -1380,14 +1261,11 @@ void k_open_fold_v2(DecodeArgs a) {
     const FileParams* Pp = a.params + (act ? f : 0);
     uint8_t* gout = DEC ? nullptr : const_cast<uint8_t*>(a.pt) + Pp->out_off;  // !DEC: plaintext in HBM
 
-    auto load_block = [&](int k) { load_block_of(cur, k); };
-    // PF: this iteration's loads were issued during the previous one.  JIT: block k - 1's loads
-    // are issued when block k starts (half the ciphertext registers); otherwise every block's
+    // PF: this iteration's loads were issued during the previous one; otherwise every block's
     // loads are issued up front.
     if (!PF) {
 #pragma unroll
-      for (int k = BPL - 1; k >= (JIT ? BPL - 1 : 0); k--)
-        if (!PF1 || k != BPL - 1) load_block(k);
+      for (int k = BPL - 1; k >= 0; k--) load_block_of(cur, k);
     }
 
     // 2) per block, earliest first: keystream (counter 1 + b) in registers, XOR, plaintext ->
@@ -1403,20 +1281,15 @@ void k_open_fold_v2(DecodeArgs a) {
     if (LPF == 32) RC = mulmod(RC, RC);  // chain step r^(4 LPF) = r^128
     L5 R2;
 #pragma unroll
-    for (int i = 0; i < 5; i++) R2.v[i] = DP ? cur.R2[i] : Pp->rpow[1][i];
+    for (int i = 0; i < 5; i++) R2.v[i] = Pp->rpow[1][i];
     const MulR M1 = mul_r(R1), M2 = mul_r(R2), M3 = mul_r(mulmod(R2, R1)), MC = mul_r(RC);
     L5 acc{{0, 0, 0, 0, 0}}, glast{{0, 0, 0, 0, 0}};
     uint32_t rp[4 * C::NRP];  // r^(2^k), k <= LOG + 1
     uint4 sv4, tg4;           // s || expected tag
-    CE_PHASE2(0)
 #pragma unroll
     for (int k = BPL - 1; k >= 0; k--) {
       const int32_t b = nblk - 1 - (int32_t)sub - LPF * k;
       const bool has = b >= 0;
-      if (JIT && k > 0) {
-        load_block(k - 1);
-        __builtin_amdgcn_sched_barrier(0);  // keep the loads here, ahead of this block's ChaCha20
-      }
       // open only: slots no file of the wave has (files under 16 x 64 B per lane slot: C3's 2 KiB
       // op files use two of the four) are skipped whole; slot 0 always has the file's last block.
       // Not in the decoding kernel: the branch splits the straight-line block sequence the
@@ -1434,13 +1307,7 @@ void k_open_fold_v2(DecodeArgs a) {
         tg4 = *reinterpret_cast<const uint4*>(Pp->tag);
       }
       uint32_t kb[16];
-#if CE_FUSED_DIAG
-      if (a.ablate & 4) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) kb[i] = cur.key[i & 7] + (uint32_t)b;
-      } else
-#endif
-        chacha_block_pre<SD, UNR>(cpre, cur.key, 1u + (uint32_t)b, 0u, cur.n2a, cur.n2b, kb);
+      chacha_block_pre<true, UNR>(cpre, cur.key, 1u + (uint32_t)b, 0u, cur.n2a, cur.n2b, kb);
       L5 G, mj[4];
 #pragma unroll
       for (int j = 0; j < 4; j++) {
@@ -1478,11 +1345,7 @@ void k_open_fold_v2(DecodeArgs a) {
         } else if (j == 0) {
           G = m;  // piece 4 b exists whenever the block does
         } else {
-#if CE_FUSED_DIAG
-          const L5 gn = (a.ablate & 2) ? add5(G, m) : add5(mulmod(G, R1), m);
-#else
           const L5 gn = add5(mulmod(G, R1), m);
-#endif
           if (k == 0) {
             const bool ex = q < npc;
 #pragma unroll
@@ -1497,32 +1360,21 @@ void k_open_fold_v2(DecodeArgs a) {
         // every block but slot 0 is full: acc r^(4 LPF) + m0 r^3 + m1 r^2 + m2 r + m3 as four
         // products into one set of column sums, carried once (vs four Horner mulmods)
         uint64_t d[5] = {mj[3].v[0], mj[3].v[1], mj[3].v[2], mj[3].v[3], mj[3].v[4]};
-#if CE_FUSED_DIAG
-        if (a.ablate & 2) {
-          an = add5(add5(acc, mj[0]), add5(add5(mj[1], mj[2]), mj[3]));
-        } else
-#endif
-        {
-          mac5(d, acc, MC);
-          mac5(d, mj[0], M3);
-          mac5(d, mj[1], M2);
-          mac5(d, mj[2], M1);
-          an = reduce5(d);
-        }
+        mac5(d, acc, MC);
+        mac5(d, mj[0], M3);
+        mac5(d, mj[1], M2);
+        mac5(d, mj[2], M1);
+        an = reduce5(d);
       } else {
         an = add5(mulmod(acc, RC), G);
       }
       const bool to_acc = has && !(k == 0 && sub == 0);
 #pragma unroll
       for (int i = 0; i < 5; i++) acc.v[i] = to_acc ? an.v[i] : acc.v[i];
-      if (PF1 && k == BPL - 1) load_block_of(nx, BPL - 1);  // next iteration's first block
       if (k == 0) {
 #pragma unroll
         for (int i = 0; i < 5; i++) glast.v[i] = has && sub == 0 ? G.v[i] : 0u;
       }
-      if (k == BPL - 1) { CE_PHASE2(1) }
-      else if (k == 1) { CE_PHASE2(2) }
-      else if (k == 0) { CE_PHASE2(3) }
     }
 
     // 3) chains -> tree positions (q takes lane q + 1's chain, q = LPF - 1 lane 0's), then
@@ -1564,11 +1416,7 @@ void k_open_fold_v2(DecodeArgs a) {
       if (!tag_ok) a.status[f] = CE_ERR_AUTH;
     }
     fails.add(act && sub == 0 && !tag_ok, f);
-    bool ok = grp_bits<LPF>(tag_ok, grp) != 0;
-#if CE_FUSED_DIAG
-    if (a.ablate) ok = !(a.ablate & 1);
-#endif
-    CE_PHASE2(4)
+    const bool ok = grp_bits<LPF>(tag_ok, grp) != 0;
 
     // 4) data-version check, decode from LDS, fold; the next iteration's parameters are loaded
     //    inside (their latency hides under the decode)
@@ -1590,33 +1438,20 @@ void k_open_fold_v2(DecodeArgs a) {
       (void)ok;
       nx = load_pre2(a, (g + stride) * F + grp);
     } else
-    decode_fold<LPF, (OPT >> 7) & 15>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, S, [&] {
+    decode_fold<LPF>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, S, [&] {
       if (PF) {
         // next iteration's ciphertext (its parameters arrived one iteration ago) into the
         // registers this iteration no longer needs, then the parameters one further ahead
 #pragma unroll
         for (int k = BPL - 1; k >= 0; k--) load_block_of(nx, k);
         nn = load_pre2(a, (g + 2 * stride) * F + grp);
-      } else if (!PF1 && !DP) {
+      } else {
         nx = load_pre2(a, (g + stride) * F + grp);
       }
     });
-    if (DP) nn = load_pre2(a, (g + 2 * stride) * F + grp);
     __builtin_amdgcn_wave_barrier();
-    CE_PHASE2(5)
-#if CE_FUSED_DIAG
-    pc[6]++;
-#endif
   }
   fails.flush(a);
-#undef CE_PHASE2
-#if CE_FUSED_DIAG
-  if (a.prof && lane == 0) {
-    unsigned long long* o = a.prof + 8ull * blockIdx.x;
-#pragma unroll
-    for (int i = 0; i < 7; i++) o[i] = pc[i];
-  }
-#endif
 }
 
 #ifndef CE_V3_UNR
@@ -1630,7 +1465,7 @@ void k_open_fold_v2(DecodeArgs a) {
 __device__ const uint32_t kPolyOne[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 
 // ----------------------------------------------------------------------------------------
-// k_open_fold_v3: k_open_fold_v2<16, 2, false, 1> (the C2 kernel) with its Poly1305 rebuilt
+// k_open_fold_v3: k_open_fold_v2<16, 2, false> (the C2 kernel before it) with its Poly1305 rebuilt
 // around the setup's per-file constants (PolyAux, ce_kernels.h), so that every Poly1305 step
 // of a lane is a four-product column sum reduced once, and the cross-lane combination is sums:
 //   - the full blocks: acc r^64 + m0 r^3 + m1 r^2 + m2 r + m3 (r^3 from the setup; the first
@@ -1852,7 +1687,7 @@ void k_open_fold_v3(DecodeArgs a) {
     // 4) data-version check, decode from LDS, fold; the next iteration's parameters are loaded
     //    inside (their latency hides under the decode)
     if (CE_V3_PRIO) __builtin_amdgcn_s_setprio(CE_V3_PRIO);  // the decode's short dependent chains first
-    decode_fold<LPF, 0, true, PN>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, S, [&] {
+    decode_fold<LPF, true, PN>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, S, [&] {
       if (!EARLY) nx = load_pre2(a, (g + 1) * F + grp);
     });
     if (CE_V3_PRIO) __builtin_amdgcn_s_setprio(0);
@@ -2070,16 +1905,16 @@ void k_open_ds8(DecodeArgs a) {
   fails.flush(a);
 }
 
-template <int LPF, int W, bool JIT, int OPT = 3, bool DEC = true, bool DS = false>
+template <int LPF, int W, bool PF, bool DEC = true, bool DS = false>
 static void launch_v2(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log, const char* key,
                       hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
-  static const uint32_t res = resident_blocks(k_open_fold_v2<LPF, W, JIT, OPT, DEC, DS>, 64);
+  static const uint32_t res = resident_blocks(k_open_fold_v2<LPF, W, PF, DEC, DS>, 64);
   const uint32_t groups = (a.n + 64 / LPF - 1) / (64 / LPF);
   const dim3 grid(log.grid(std::min<uint32_t>(groups, res), key));
   if (t0) {  // the launch's own start / end timestamps: no marker packets around the kernel
-    hipExtLaunchKernelGGL((k_open_fold_v2<LPF, W, JIT, OPT, DEC, DS>), grid, dim3(64), 0, s, t0, t1, 0u, a);
+    hipExtLaunchKernelGGL((k_open_fold_v2<LPF, W, PF, DEC, DS>), grid, dim3(64), 0, s, t0, t1, 0u, a);
   } else {
-    hipLaunchKernelGGL((k_open_fold_v2<LPF, W, JIT, OPT, DEC, DS>), grid, dim3(64), 0, s, a);
+    hipLaunchKernelGGL((k_open_fold_v2<LPF, W, PF, DEC, DS>), grid, dim3(64), 0, s, a);
   }
 }
 
@@ -2109,11 +1944,11 @@ hipError_t launch_open_small_v2(hipStream_t s, const DecodeArgs& a, OpenLaunchLo
     }
     DecodeArgs b = a;
     b.only = a.ds.big;
-    launch_v2<16, 3, false, 1, false, true>(s, b, log, "open_ds16");
+    launch_v2<16, 3, false, false, true>(s, b, log, "open_ds16");
   } else if (a.ds.on) {
-    launch_v2<16, 3, false, 1, false, true>(s, a, log, "open_ds16");
+    launch_v2<16, 3, false, false, true>(s, a, log, "open_ds16");
   } else {
-    launch_v2<16, 3, false, 1, false>(s, a, log, "open_only_lpf16");
+    launch_v2<16, 3, false, false>(s, a, log, "open_only_lpf16");
   }
   return hipGetLastError();
 }
@@ -2155,50 +1990,10 @@ hipError_t launch_open_fold_v2(hipStream_t s, const DecodeArgs& a, int files_per
     }
     return hipGetLastError();
   }
-#if CE_FUSED_DIAG
-  // diagnostics build only (libcrdtenc_prof.so): same-box A/B variants.  Several of them are
-  // NOT correct (OPT 129/385 skip the actor lookups, 513/1025 may write status 77), so none is
-  // compiled into the product library, which ignores both variables.
-  // CE_V2_WAVES: 3 = 3 waves/SIMD VGPR budget, 13 = 3 with JIT ciphertext loads, 12 = 2 with
-  // them; 4 = 4 waves at 2 files per wave.  CE_V2_OPT: the OPT bits of the LPF 16 kernel.
-  static const int w = [] {
-    const char* e = getenv("CE_V2_WAVES");
-    return e ? atoi(e) : 0;
-  }();
-  static const int opt = [] {
-    const char* e = getenv("CE_V2_OPT");
-    return e ? atoi(e) : 1;
-  }();
-  if (files_per_wave == 2) {
-    if (w == 4) launch_v2<32, 4, false>(s, a, log, "open_v2_lpf32", t0, t1);
-    else launch_v2<32, 3, false>(s, a, log, "open_v2_lpf32", t0, t1);
-  } else {
-    if (w == 3) launch_v2<16, 3, false>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (w == 13) launch_v2<16, 3, true>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (w == 12) launch_v2<16, 2, true>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 0) launch_v2<16, 2, false, 0>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 1) launch_v2<16, 2, false, 1>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 2) launch_v2<16, 2, false, 2>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 5) launch_v2<16, 2, false, 5>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 9) launch_v2<16, 2, false, 9>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 17) launch_v2<16, 2, false, 17>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 21) launch_v2<16, 2, false, 21>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 33) launch_v2<16, 2, false, 33>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 65) launch_v2<16, 2, false, 65>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 129) launch_v2<16, 2, false, 129>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 257) launch_v2<16, 2, false, 257>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 385) launch_v2<16, 2, false, 385>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 513) launch_v2<16, 2, false, 513>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 1025) launch_v2<16, 2, false, 1025>(s, a, log, "open_v2_lpf16", t0, t1);
-    else if (opt == 81) launch_v2<16, 2, false, 81>(s, a, log, "open_v2_lpf16", t0, t1);
-    else launch_v2<16, 2, false, 3>(s, a, log, "open_v2_lpf16", t0, t1);
-  }
-#else
-  // product: the measured default only -- SDWA rot16 on, next-ciphertext prefetch off (same-box
-  // A/B r02); 2 files per wave at a 3-wave budget (SDWA rot16 + prefetch) for the fpw = 2 geometry
-  if (files_per_wave == 2) launch_v2<32, 3, false, 3>(s, a, log, "open_v2_lpf32", t0, t1);
-  else launch_v2<16, 2, false, 1>(s, a, log, "open_v2_lpf16", t0, t1);
-#endif
+  // the measured defaults: next-ciphertext prefetch off at 4 files per wave (same-box A/B r02);
+  // 2 files per wave at a 3-wave budget with the prefetch for the fpw = 2 geometry
+  if (files_per_wave == 2) launch_v2<32, 3, true>(s, a, log, "open_v2_lpf32", t0, t1);
+  else launch_v2<16, 2, false>(s, a, log, "open_v2_lpf16", t0, t1);
   return hipGetLastError();
 }
 

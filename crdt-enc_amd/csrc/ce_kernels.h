@@ -153,9 +153,6 @@ struct DecodeArgs {
   uint8_t* refold;              // per file: had a miss
   const uint8_t* only;          // null, or per-file: process only files with only[i] != 0
   int large_only;               // skip files the fused kernel handles (iterate large_list)
-  int ablate;                   // diagnostics only (CE_ABLATE): 1 no decode, 2 no Poly1305,
-                                // 4 no ChaCha20, 8 no ciphertext loads -- results invalid
-  unsigned long long* prof;     // diagnostics only (CE_PROF): per-wave phase cycles, 8 per wave
   const uint32_t* large_list;
   const uint8_t* blob;          // fused kernel: input files (ciphertext at FileParams.in_off)
   uint8_t* redo;                // k_segdec_apply: files left to the whole-file decode

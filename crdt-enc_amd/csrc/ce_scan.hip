@@ -1,7 +1,7 @@
-// ce_scan.hip -- device-wide exclusive scans for the dot-set path, in place of hipCUB's.
+// ce_scan.hip -- device-wide exclusive scans for the dot-set path.
 //
-// hipCUB's DeviceScan (rocPRIM's look-back scan) queries the device properties on the host at
-// every call (to pick a sleep variant of its look-back state for one older chip); in the HIP
+// rocPRIM's look-back DeviceScan, used here at first, queries the device properties on the host
+// at every call (to pick a sleep variant of its look-back state for one older chip); in the HIP
 // runtime torch loads that query costs tens of microseconds, which a C3 step paid ~5 times while
 // the GPU waited for the next launch (profiles/r04_c3_step.txt).  These scans are plain launches
 // over 2048-item tiles: tile totals, then the tiles rescanned with their offsets (each block
@@ -10,11 +10,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#if CE_FUSED_DIAG  // hipCUB only for the diagnostics build's A/B (CE_HIPCUB_SCAN)
-#include <hipcub/hipcub.hpp>
-#endif
-
-#include <algorithm>
 #include <cstdlib>
 
 #include "ce_dotset.h"
@@ -307,18 +302,6 @@ __global__ void __launch_bounds__(kB) k_seg_apply_direct(const uint32_t* keys, c
 }  // namespace
 
 namespace {
-struct MaxOp {
-  __device__ __host__ unsigned long long operator()(unsigned long long a, unsigned long long b) const { return a > b ? a : b; }
-};
-// CE_HIPCUB_SCAN=1 (diagnostics build only): hipCUB's scans instead, for same-box A/B
-bool use_hipcub() {
-#if CE_FUSED_DIAG
-  static const bool v = getenv("CE_HIPCUB_SCAN") != nullptr;
-  return v;
-#else
-  return false;
-#endif
-}
 // CE_SCAN_3PASS=1 (tests): the three-launch form (tile sums, one carry block, apply) at any size;
 // by default it only runs past kApplyScanTiles tiles
 bool three_pass() {
@@ -328,14 +311,6 @@ bool three_pass() {
 }  // namespace
 
 hipError_t ds_excl_sum_u32(void* tmp, size_t& tb, const uint32_t* in, uint32_t* out, uint32_t n, hipStream_t s) {
-#if CE_FUSED_DIAG
-  if (use_hipcub()) {
-    size_t need = 0;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, in, out, (int)n, s);
-    if (!tmp) { tb = std::max<size_t>(need, 4ull * (tiles_for(n) + 1) + 64); return e; }
-    return hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, (int)n, s);
-  }
-#endif
   const uint32_t nt = tiles_for(n);
   const size_t need = 4ull * (nt + 1) + 64;
   if (!tmp) {
@@ -357,16 +332,6 @@ hipError_t ds_excl_sum_u32(void* tmp, size_t& tb, const uint32_t* in, uint32_t* 
 
 hipError_t ds_excl_max_by_key(void* tmp, size_t& tb, const uint32_t* keys, const unsigned long long* vals,
                               unsigned long long* out, uint32_t n, hipStream_t s) {
-#if CE_FUSED_DIAG
-  if (use_hipcub()) {
-    size_t need = 0;
-    hipError_t e = hipcub::DeviceScan::ExclusiveScanByKey(nullptr, need, keys, vals, out, MaxOp(), 0ull, (int)n,
-                                                          hipcub::Equality(), s);
-    if (!tmp) { tb = std::max<size_t>(need, sizeof(Seg) * (tiles_for(n) + 1) + 64); return e; }
-    return hipcub::DeviceScan::ExclusiveScanByKey(tmp, tb, keys, vals, out, MaxOp(), 0ull, (int)n,
-                                                  hipcub::Equality(), s);
-  }
-#endif
   const uint32_t nt = tiles_for(n);
   const size_t need = sizeof(Seg) * (nt + 1) + 64;
   if (!tmp) {

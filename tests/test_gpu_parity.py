@@ -1140,9 +1140,10 @@ def test_clock_probe(ctx):
 
 @pytest.mark.gpu
 def test_diag_env_cannot_select_wrong_variants():
-    """CE_V2_OPT=129 (actor lookups skipped, wrong results on purpose) and CE_V2_WAVES=13 select
-    diagnostics variants only in libcrdtenc_prof.so; the product library ignores them, so
-    __graft_entry__.smoke() run with them set still folds to the oracle's state."""
+    """CE_V2_OPT=129 (actor lookups skipped, wrong results on purpose) and CE_V2_WAVES=13 once
+    selected diagnostics variants of k_open_fold_v2 in a second build of the library.  That build
+    is gone and no code reads either variable any more: __graft_entry__.smoke() run with them
+    set still folds to the oracle's state."""
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of env knobs on the full bench line (no CPU leg): one line per run.  A run whose
-# result check fails (diagnostic variants) still prints its times, marked CHECK-FAILED.
-#   AB="CE_V2_OPT=1 CE_V2_OPT=3" BENCH_ARGS="--no-variant-b" tools/gpu_ab.sh
+# result check fails still prints its times, marked CHECK-FAILED.
+#   AB="CE_V3=2 CE_V3=3" BENCH_ARGS="--no-variant-b" tools/gpu_ab.sh
 cd "$(dirname "$0")/.."
 OUT=${OUT:-bench_out}
 mkdir -p $OUT
