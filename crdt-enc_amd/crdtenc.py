@@ -26,6 +26,7 @@ ERR_OP_VERSION, ERR_SHARD = 13, 69
 # window flags word (hi[m], include/crdtenc.h ce_core_shard_window)
 SHARD_BAD, SHARD_GAP, SHARD_E0_MISMATCH = 1, 2, 4
 STATE_VCLOCK, STATE_GCOUNTER, STATE_ORSWOT, STATE_MVREG, STATE_PNCOUNTER = 0, 1, 2, 3, 4
+STATE_GSET = 5
 OPEN_CREATE, COMPACT_INGEST_FORMAT, OPEN_MULTI_KEY = 1, 2, 4
 
 CORE_VERSION = bytes.fromhex("e834d789101b463498239de990a9051f")   # crdt-enc/src/lib.rs:26
@@ -611,7 +612,7 @@ class Keys:
 
 class Core:
     """Core<S> for S in {VClock<Uuid>, GCounter<Uuid>, Orswot<u64, Uuid>, MVReg<u64, Uuid>,
-    PNCounter<Uuid>} (crdt-enc/src/lib.rs)."""
+    PNCounter<Uuid>, GSet<u64>} (crdt-enc/src/lib.rs)."""
 
     def __init__(self, ctx, kind=STATE_GCOUNTER, supported=(), current_data_version=None,
                  local_path=None, remote_path=None, flags=0):

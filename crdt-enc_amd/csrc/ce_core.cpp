@@ -1,6 +1,8 @@
 // ce_core.cpp -- Core<S, Storage, Cryptor, _> (crdt-enc/src/lib.rs:188-723), driving the GPU
 // batch engine.  S = VClock<Uuid> / GCounter<Uuid> / PNCounter<Uuid> live here; S = Orswot<u64, Uuid> /
-// MVReg<u64, Uuid> (the dot-set kinds) dispatch to ce_dotset_host.cpp.
+// MVReg<u64, Uuid> (the dot-set kinds) dispatch to ce_dotset_host.cpp, S = GSet<u64> to
+// ce_gset_host.cpp (its members live in a device hash set; the actor table and next_op_versions
+// below are shared).
 //
 // State layout: a host-built open-addressing actor table (UUID -> dense slot) mirrored in HBM;
 // the CRDT state (VClock dots / GCounter.inner) is a dense u64[cap] max-register array in HBM
@@ -155,10 +157,13 @@ bool read_vclock(Rd& r, Dots* out) {
 
 // StateWrapper<S> { next_op_versions: VClock, state: S } (lib.rs:739-743)
 // stn (PNCounter): the n counter's dots; state = { p: GCounter, n: GCounter }
-bool read_state_wrapper(const uint8_t* p, size_t n, int kind, Dots* nov, Dots* st, Dots* stn) {
+// members (GSet): the `value` form, state = { value: BTreeSet<u64> }
+bool read_state_wrapper(const uint8_t* p, size_t n, int kind, Dots* nov, Dots* st, Dots* stn,
+                        std::vector<uint64_t>* members = nullptr) {
   Rd r{p, n, 0};
   return read_struct(r, {"next_op_versions", "state"}, [&](int f, Rd& q) {
     if (f == 0) return read_vclock(q, nov);
+    if (kind == CE_STATE_GSET) return read_gset_state(q, members);
     if (kind == CE_STATE_PNCOUNTER)
       return read_struct(q, {"p", "n"}, [&](int g, Rd& q2) {
         return read_struct(q2, {"inner"}, [&](int, Rd& q3) { return read_vclock(q3, g == 0 ? st : stn); });
@@ -443,13 +448,42 @@ void ensure_sorted(ce_core* c) {
   c->sorted_gen = c->table_gen;
 }
 
-int serialize_state(ce_core* c, std::vector<uint8_t>* out) {
+// (GSet only) head_only: stop after a5"state", the part the host writes before the device writer's;
+// prefix16: an ingest-format compaction's data version in front of it
+int serialize_state(ce_core* c, std::vector<uint8_t>* out, bool head_only = false,
+                    const uint8_t* prefix16 = nullptr) {
   if (is_dotset_kind(c->kind)) return ds_serialize(c, out);
   std::vector<uint64_t> st;
-  int rc = download_state(c, &st);
+  int rc = c->kind == CE_STATE_GSET ? CE_OK : download_state(c, &st);  // (GSet: no dense state)
   if (rc) return rc;
   ensure_sorted(c);
   const std::vector<uint32_t>& slots = c->sorted_slots;
+  if (c->kind == CE_STATE_GSET) {  // next_op_versions as below, then { value: the sorted members }
+    size_t n_nov = 0;
+    for (uint32_t s : slots) n_nov += c->nov[s] != 0;
+    Wr w;
+    w.b.swap(*out);
+    w.b.clear();
+    if (prefix16) w.b.insert(w.b.end(), prefix16, prefix16 + 16);
+    w.map(2);
+    w.str("next_op_versions");
+    w.map(1);
+    w.str("dots");
+    w.map(n_nov);
+    for (uint32_t s : slots)
+      if (c->nov[s]) { w.bin(c->slot_actor[s].data(), 16); w.uint(c->nov[s]); }
+    w.str("state");
+    if (head_only) {  // the device writer continues from here
+      out->swap(w.b);
+      return CE_OK;
+    }
+    if (!c->host_compact) return gs_serialize_device(c, std::move(w.b), out);
+    std::vector<uint64_t> members;  // CE_HOST_COMPACT=1: the host writer, the device writer's cross-check
+    if ((rc = gs_members_sorted(c, &members))) return rc;
+    write_gset_state(&w, members);
+    out->swap(w.b);
+    return CE_OK;
+  }
   const bool pnc = c->kind == CE_STATE_PNCOUNTER;
   size_t n_nov = 0, n_st = 0, n_neg = 0;
   for (uint32_t s : slots) { n_nov += c->nov[s] != 0; n_st += st[s] != 0; }
@@ -718,6 +752,8 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
   if (n == 0) return CE_OK;
   if (is_dotset_kind(c->kind))
     return ds_ingest_ops(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, status_out);
+  if (c->kind == CE_STATE_GSET)
+    return gs_ingest_ops(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, status_out);
   hipError_t e;
   const KeyRef key = key_of(c);
   const bool pnc = c->kind == CE_STATE_PNCOUNTER;
@@ -1324,6 +1360,7 @@ int ingest_states_dev(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs,
   // host pass: StateWrapper msgpack -> dots (north star: "host pass that flattens decoded
   // ops/states into columnar arrays")
   std::vector<Dots> novs(n), sts(n), negs(n);  // negs: PNCounter's n plane
+  std::vector<uint64_t> members;               // GSet: every file's `value`, one column
   int first = CE_OK;
   for (uint32_t i = 0; i < n; i++) {
     if (st[i] == CE_OK) {
@@ -1334,7 +1371,7 @@ int ingest_states_dev(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs,
         Uuid v;
         std::memcpy(v.data(), pt, 16);
         if (!std::binary_search(c->supported.begin(), c->supported.end(), v)) st[i] = CE_ERR_PT_VERSION;
-        else if (!read_state_wrapper(pt + 16, len - 16, c->kind, &novs[i], &sts[i], &negs[i]))
+        else if (!read_state_wrapper(pt + 16, len - 16, c->kind, &novs[i], &sts[i], &negs[i], &members))
           st[i] = CE_ERR_DECODE;
       }
     }
@@ -1348,7 +1385,7 @@ int ingest_states_dev(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs,
     all.insert(all.end(), sts[i].begin(), sts[i].end());
     alln.insert(alln.end(), negs[i].begin(), negs[i].end());
   }
-  if ((rc = merge_dots_host(c, all, &alln))) return rc;
+  if ((rc = c->kind == CE_STATE_GSET ? gs_insert_members(c, members) : merge_dots_host(c, all, &alln))) return rc;
   for (uint32_t i = 0; i < n; i++)
     for (auto& d : novs[i]) {
       uint32_t s;
@@ -1546,6 +1583,15 @@ int compact_device(ce_core* c, const uint8_t* nonce, std::vector<uint8_t>* file)
 int compact_bytes(ce_core* c, const uint8_t* nonce, std::vector<uint8_t>* file) {
   HostPhase hp("compact_bytes");
   if (!c->has_key) return c->ctx->fail(CE_ERR_NO_KEY, "no latest key");
+  if (c->kind == CE_STATE_GSET && !c->host_compact) {
+    // the members sorted, encoded and sealed on the device; the host writes next_op_versions
+    const bool ingest_fmt = (c->flags & CE_COMPACT_INGEST_FORMAT) != 0;
+    std::vector<uint8_t> head;
+    int rc = serialize_state(c, &head, true, ingest_fmt ? c->current_data_version.data() : nullptr);
+    if (rc) return rc;
+    return gs_compact_device(c, std::move(head), ingest_fmt ? kCoreVersion : c->current_data_version.data(),
+                             nonce, key_of(c), file);
+  }
   if (!is_dotset_kind(c->kind) && !c->host_compact) return compact_device(c, nonce, file);
   if (c->kind == CE_STATE_ORSWOT && !c->host_compact) {
     // entries serialized, sealed and downloaded once on the device (ce_dotset_io.hip)
@@ -1573,7 +1619,7 @@ int ce_core_open(ce_ctx* ctx, const ce_open_options* o, ce_core** out) {
   if (!ctx || !o || !out || !o->current_data_version || (o->n_supported && !o->supported_data_versions))
     return CE_ERR_INVALID_ARG;
   if (o->state_kind != CE_STATE_VCLOCK && o->state_kind != CE_STATE_GCOUNTER &&
-      o->state_kind != CE_STATE_PNCOUNTER && !is_dotset_kind(o->state_kind))
+      o->state_kind != CE_STATE_PNCOUNTER && o->state_kind != CE_STATE_GSET && !is_dotset_kind(o->state_kind))
     return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(ctx->mu);
   (void)hipSetDevice(ctx->device);
@@ -1600,6 +1646,7 @@ int ce_core_open(ce_ctx* ctx, const ce_open_options* o, ce_core** out) {
   int rc = table_init(c, 8192);
   if (rc) { delete c; return rc; }
   if (is_dotset_kind(c->kind) && (rc = ds_init(c))) { ce_core_close(c); return rc; }
+  if (c->kind == CE_STATE_GSET && (rc = gs_init(c))) { ce_core_close(c); return rc; }
   if (o->local_path || o->remote_path) {
     if (!o->local_path || !o->remote_path || o->local_path[0] != '/' || o->remote_path[0] != '/') {
       delete c;
@@ -1660,6 +1707,7 @@ void ce_core_close(ce_core* c) {
   delete c->storage;
   delete c->aux;
   ds_free(c->ds);
+  gs_free(c->gs);
   delete c;
 }
 
@@ -1766,7 +1814,7 @@ static int compact_ops_device_impl(ce_core* c, const uint8_t* d_blob, const uint
   std::vector<uint8_t>& f = c->file_buf;
   int rc;
   bool merged = false;
-  const bool spec = !is_dotset_kind(c->kind) && !c->host_compact && n > 0;
+  const bool spec = !is_dotset_kind(c->kind) && c->kind != CE_STATE_GSET && !c->host_compact && n > 0;
   ce_ctx* x = aux_ctx(c);  // same stream: the compaction is ordered behind the ingest
   CompactPending pend;
   uint8_t nb[24];  // one nonce for the speculative and (if needed) the repeated compaction
@@ -2039,10 +2087,13 @@ int ce_core_apply_ops(ce_core* c, const uint8_t* ops, size_t len) {
   (void)hipSetDevice(c->ctx->device);
   if (!c->has_key) return c->ctx->fail(CE_ERR_NO_KEY, "no latest key");
   Dots dots, neg;  // neg: a PNCounter's Neg ops
-  const bool ds = is_dotset_kind(c->kind);
+  std::vector<uint64_t> members;  // a GSet's ops
+  const bool ds = is_dotset_kind(c->kind), gs = c->kind == CE_STATE_GSET;
   if (ds) {
     int rc = ds_check_ops(c, ops, len);
     if (rc) return rc;
+  } else if (gs) {
+    if (!parse_gset_ops(ops, len, &members)) return c->ctx->fail(CE_ERR_DECODE, "ops are not a Vec<u64>");
   } else if (c->kind == CE_STATE_PNCOUNTER) {
     if (!read_pn_ops(ops, len, &dots, &neg)) return c->ctx->fail(CE_ERR_DECODE, "ops are not a Vec<pncounter::Op<Uuid>>");
   } else if (!read_dots(ops, len, &dots)) {
@@ -2060,7 +2111,9 @@ int ce_core_apply_ops(ce_core* c, const uint8_t* ops, size_t len) {
   if (c->storage && (rc = storage_store_op(c->storage, c->local_actor, version, file.data(), file.size())))
     return c->ctx->fail(rc, "failed writing ops file");
   // state.apply(op) for op in ops (lib.rs:710-712)
-  if ((rc = ds ? ds_apply_local_ops(c, ops, len) : merge_dots_host(c, dots, &neg))) return rc;
+  if ((rc = ds ? ds_apply_local_ops(c, ops, len)
+               : gs ? gs_insert_members(c, members) : merge_dots_host(c, dots, &neg)))
+    return rc;
   // the apply may have grown the table (new Dot actors), which moves every slot: look it up again
   s = c->slot_of.at(c->local_actor);
   c->nov[s] = version + 1;                         // next_op_versions.inc(actor) (lib.rs:714-715)
@@ -2079,13 +2132,17 @@ int ce_core_apply_ops_batch(ce_core* c, const uint8_t* ops, const uint64_t* offs
   ce_ctx* ctx = c->ctx;
   if (!c->has_key) return ctx->fail(CE_ERR_NO_KEY, "no latest key");
   const bool ds = is_dotset_kind(c->kind);
+  const bool gs = c->kind == CE_STATE_GSET;
   std::vector<Dots> dots(ds ? 0 : n), negs(ds ? 0 : n);
+  std::vector<std::vector<uint64_t>> members(gs ? n : 0);  // a GSet's ops
   for (uint32_t i = 0; i < n; i++) {
     const uint8_t* p = ops + offs[i];
     const size_t l = offs[i + 1] - offs[i];
     if (ds) {
       int rc = ds_check_ops(c, p, l);
       if (rc) return rc;
+    } else if (gs) {
+      if (!parse_gset_ops(p, l, &members[i])) return ctx->fail(CE_ERR_DECODE, "ops are not a Vec<u64>");
     } else if (c->kind == CE_STATE_PNCOUNTER) {
       if (!read_pn_ops(p, l, &dots[i], &negs[i]))
         return ctx->fail(CE_ERR_DECODE, "ops are not a Vec<pncounter::Op<Uuid>>");
@@ -2143,7 +2200,7 @@ int ce_core_apply_ops_batch(ce_core* c, const uint8_t* ops, const uint64_t* offs
       return ctx->fail(rc, "failed writing ops file");
     // state.apply(op) for op in ops (lib.rs:710-712), then next_op_versions.inc (lib.rs:714-715)
     if ((rc = ds ? ds_apply_local_ops(c, ops + offs[i], offs[i + 1] - offs[i])
-                 : merge_dots_host(c, dots[i], &negs[i])))
+                 : gs ? gs_insert_members(c, members[i]) : merge_dots_host(c, dots[i], &negs[i])))
       return rc;
     s = c->slot_of.at(c->local_actor);  // a growth inside the apply moved the local actor's slot
     c->nov[s] = v0 + i + 1;
@@ -2167,6 +2224,7 @@ int ce_core_reset(ce_core* c) {
   std::fill(c->nov.begin(), c->nov.end(), 0);
   c->read_states.clear();
   if (is_dotset_kind(c->kind)) return ds_reset(c);  // (the dense state array is the VClock kinds')
+  if (c->kind == CE_STATE_GSET) return gs_reset(c);
   hipError_t e = hipMemsetAsync(c->d_state.p, 0, (uint64_t)state_planes(c->kind) * c->cap * 8ull, c->ctx->stream);
   if (e) return c->ctx->hip_fail(e, "reset");
   return CE_OK;
@@ -2176,6 +2234,7 @@ int ce_core_settle(ce_core* c) {
   if (!c) return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
   if (is_dotset_kind(c->kind)) return ds_settle(c);
+  if (c->kind == CE_STATE_GSET) return gs_settle(c);
   hipError_t e = hipStreamSynchronize(c->ctx->stream);
   if (e) return c->ctx->hip_fail(e, "settle");
   return CE_OK;
@@ -2252,9 +2311,11 @@ int ce_core_merge_state(ce_core* c, const uint8_t* sw, size_t len) {
     return ds_merge_states(c, sws, &st, nullptr);
   }
   Dots nov, state, neg;
-  if (!read_state_wrapper(sw, len, c->kind, &nov, &state, &neg))
+  std::vector<uint64_t> members;  // a GSet's `value`
+  if (!read_state_wrapper(sw, len, c->kind, &nov, &state, &neg, &members))
     return c->ctx->fail(CE_ERR_DECODE, "not a StateWrapper");
-  int rc = merge_dots_host(c, state, &neg);  // state.merge(sw.state) (lib.rs:460)
+  // state.merge(sw.state) (lib.rs:460)
+  int rc = c->kind == CE_STATE_GSET ? gs_insert_members(c, members) : merge_dots_host(c, state, &neg);
   if (rc) return rc;
   for (auto& d : nov) {                // next_op_versions.merge(..) (lib.rs:461-463)
     uint32_t s;

@@ -33,11 +33,15 @@ ce_storage* storage_new(const std::string& local, const std::string& remote);
 
 struct DsState;  // Orswot / MVReg state (ce_dotset_host.cpp)
 void ds_free(DsState* d);
+struct GsState;  // GSet<u64> state: the device hash set (ce_gset_host.cpp)
+void gs_free(GsState* g);
 
 inline bool is_dotset_kind(int kind) { return kind == CE_STATE_ORSWOT || kind == CE_STATE_MVREG; }
 // kinds without the dense multi-GPU exchange (export / import / sharded ingest / pending batch):
 // their ranks exchange state bytes instead
-inline bool no_dense_exchange(int kind) { return is_dotset_kind(kind) || kind == CE_STATE_PNCOUNTER; }
+inline bool no_dense_exchange(int kind) {
+  return is_dotset_kind(kind) || kind == CE_STATE_PNCOUNTER || kind == CE_STATE_GSET;
+}
 // planes of the dense state and batch (u64[planes * cap]): PNCounter keeps p at [slot] and n at
 // [slot + cap]; next_op_versions is one plane for every kind
 inline uint32_t state_planes(int kind) { return kind == CE_STATE_PNCOUNTER ? 2u : 1u; }
@@ -119,6 +123,7 @@ struct ce_core {
   std::set<std::string> read_states;  // lib.rs:205
   ce_ctx* aux = nullptr;              // single-file work during a batch (exotic envelopes)
   ce::DsState* ds = nullptr;          // Orswot / MVReg state (dot-set kinds only)
+  ce::GsState* gs = nullptr;          // GSet state (CE_STATE_GSET only)
   // sharded ingest (ce_core_ingest_ops_device_sharded): the batch is folded into d_batch and
   // held there with its next_op_versions until ce_core_pending_commit
   bool pending = false;
@@ -263,5 +268,30 @@ int ds_merge_columns_device(ce_core* c, const uint8_t* const* parts, const uint6
 // Core::apply_ops for a local Vec<S::Op> (already validated by ds_check_ops)
 int ds_check_ops(ce_core* c, const uint8_t* ops, size_t len);
 int ds_apply_local_ops(ce_core* c, const uint8_t* ops, size_t len);
+
+// GSet<u64> (ce_gset_host.cpp): the members live in a device hash set; next_op_versions, the
+// actor table and the storage plumbing are ce_core.cpp's, as for every kind
+int gs_init(ce_core* c);
+int gs_reset(ce_core* c);
+int gs_settle(ce_core* c);
+int gs_ingest_ops(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n,
+                  uint64_t blob_len, const uint8_t* actors, uint32_t m, const uint32_t* d_fa,
+                  const uint64_t* d_fv, int32_t* status_out);
+// members (a state file's `value`, a local Vec<u64>) into the committed set
+int gs_insert_members(ce_core* c, const std::vector<uint64_t>& members);
+// the set in BTreeSet order: collected and sorted on the device
+int gs_members_sorted(ce_core* c, std::vector<uint64_t>* out);
+// the device writer.  head: the clear text up to and including a5"state" (an ingest-format
+// compaction's data version, next_op_versions); the members are collected, sorted, sized,
+// scanned and written after it on the device.  gs_serialize_device downloads the clear text;
+// gs_compact_device seals it there (file = outer || Cryptor::encrypt(clear)) and downloads the file
+int gs_serialize_device(ce_core* c, std::vector<uint8_t> head, std::vector<uint8_t>* out);
+int gs_compact_device(ce_core* c, std::vector<uint8_t> head, const uint8_t* outer, const uint8_t* nonce,
+                      const KeyRef& key, std::vector<uint8_t>* file);
+// Vec<u64> as rmp-serde reads it (any non-negative integer form); false: CE_ERR_DECODE
+bool parse_gset_ops(const uint8_t* p, size_t n, std::vector<uint64_t>* out);
+// GSet { value: BTreeSet<u64> }: the reader (any order, duplicates) and the canonical writer
+bool read_gset_state(Rd& r, std::vector<uint64_t>* out);
+void write_gset_state(Wr* w, const std::vector<uint64_t>& sorted_members);
 
 }  // namespace ce

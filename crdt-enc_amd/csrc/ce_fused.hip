@@ -20,6 +20,7 @@
 #include <hip/hip_ext.h>
 
 #include "ce_device.h"
+#include "ce_gset_device.h"
 
 namespace ce {
 
@@ -1462,6 +1463,167 @@ void k_open_fold_v2(DecodeArgs a) {
 #endif                // chains issue ahead of the other wave's ChaCha20 (C2-B -10%, C2 flat)
 // the Poly1305 value 1 in radix-2^26 limbs (k_open_fold_v3's weight of the lanes at q & 3 = 0 /
 // q >> 2 = 0, read like the other weights)
+// ---- GSet<u64> op files decoded in the open (k_open_fold_v3's GS form) ----------------------
+// The third grammar beside Dot and PN: the body is a bare Vec<u64> (ce_gset.hip has the element
+// grammar), decoded from the file's plaintext in LDS by its 16 lanes; members of gated files go
+// to the hash tables of a.gs (gs_put: the committed table read-only, absent members claimed in
+// the batch table).  Every byte used lies below the file's own length: an element is checked
+// against blen before its window is read, so what an earlier group left in the region is never
+// taken for this file's.
+struct GsCounts {  // files by path, per lane (sub == 0 counts its group's), flushed once per wave
+  uint32_t uni = 0, gen = 0;
+  __device__ __forceinline__ void flush(const DecodeArgs& a) const {
+    uint32_t u = uni, g = gen;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      u += (uint32_t)__shfl_xor((int)u, d);
+      g += (uint32_t)__shfl_xor((int)g, d);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      if (u) atomicAdd(&a.gs->paths[0], u);
+      if (g) atomicAdd(&a.gs->paths[1], g);
+      if (u + g) atomicAdd(&a.gs->paths[2], u + g);
+    }
+  }
+};
+
+// the element at byte p of the body (p < blen): its encoded length (0: not a u64, or cut short by
+// the file's end) and value.  One 12-byte window: four aligned LDS dwords, alignbyte into place.
+__device__ __forceinline__ uint32_t gs_elem_lds(const uint32_t* L, uint32_t blen, uint32_t p,
+                                                unsigned long long* out) {
+  const LdsWin<3> W(L, p);
+  const uint32_t m = W.byte(0);
+  if (m <= 0x7f) {
+    *out = m;
+    return 1;
+  }
+  if (m < 0xcc || m > 0xd3) return 0;
+  const uint32_t wd = 1u << ((m - 0xcc) & 3);
+  if (blen - p - 1 < wd) return 0;
+  const uint32_t x0 = __builtin_bswap32(W.word(1)), x1 = __builtin_bswap32(W.word(5));
+  const unsigned long long x = wd == 8 ? ((unsigned long long)x0 << 32) | x1 : (unsigned long long)(x0 >> (32 - 8 * wd));
+  if (m >= 0xd0 && ((x >> (8 * wd - 1)) & 1)) return 0;  // a negative integer
+  *out = x;
+  return 1 + wd;
+}
+
+template <int LPF, typename Pf>
+__device__ __forceinline__ void decode_gset_lds(const DecodeArgs& a, const SupVers& sup, const uint8_t* fl,
+                                                uint32_t len, bool live, bool apply, uint32_t f,
+                                                uint32_t grp, uint32_t sub, GsCounts& C, Pf&& prefetch) {
+  int32_t st = CE_OK;
+  if (live) {
+    if (len < 16) st = CE_ERR_PT_LEN;
+    else if (!sup.has(a, *reinterpret_cast<const uint4*>(fl))) st = CE_ERR_PT_VERSION;
+  }
+  const uint8_t* body = fl + 16;
+  const uint32_t* L = reinterpret_cast<const uint32_t*>(body);
+  const uint32_t blen = len >= 16 ? len - 16 : 0;
+  uint32_t cnt = 0, h = 0;
+  if (live && st == CE_OK) {
+    if (blen == 0) st = CE_ERR_DECODE;
+    else {
+      const uint32_t m = body[0];
+      if ((m & 0xf0) == 0x90) { cnt = m & 15; h = 1; }
+      else if (m == 0xdc && blen >= 3) { cnt = (uint32_t)body[1] << 8 | body[2]; h = 3; }
+      else if (m == 0xdd && blen >= 5) {
+        cnt = (uint32_t)body[1] << 24 | (uint32_t)body[2] << 16 | (uint32_t)body[3] << 8 | body[4];
+        h = 5;
+      } else st = CE_ERR_DECODE;
+      if (st == CE_OK && cnt > blen - h) st = CE_ERR_DECODE;  // each element takes >= 1 byte
+    }
+  }
+  prefetch();
+  const bool dec = live && st == CE_OK;
+  const bool ins = dec && apply;
+  const GsFused* G = a.gs;
+  // uniform width: the first element's marker gives w0 and count x w0 fits; lane `sub` checks the
+  // marker of each element it takes (sub, sub + 16, ...).  Nothing is read as a member before
+  // every lane of the group has found its markers right.
+  uint32_t w0 = 0, mk = 0;
+  if (dec && cnt > 0) {
+    mk = body[h];
+    w0 = mk <= 0x7f ? 1u : (mk >= 0xcc && mk <= 0xcf) ? 1u + (1u << (mk - 0xcc)) : 0u;
+    if (w0 && (unsigned long long)cnt * w0 > blen - h) w0 = 0;
+  }
+  bool bad = dec && cnt > 0 && w0 == 0;
+  if (w0)
+    for (uint32_t e = sub; e < cnt && !bad; e += LPF) {
+      const uint32_t m = body[h + e * w0];
+      bad = w0 == 1 ? m > 0x7f : m != mk;
+    }
+  const bool general = dec && grp_bits<LPF>(bad, grp) != 0;
+  if (dec && sub == 0) {
+    C.uni += general ? 0u : 1u;
+    C.gen += general ? 1u : 0u;
+  }
+  if (ins && !general) {
+    // four elements of the lane at a time: their first probes of both tables are issued together
+    // (eight independent loads in flight; one element at a time left the kernel waiting on each
+    // probe in turn at 2 waves per SIMD).  A first probe that finds the key settles the element;
+    // anything else takes gs_put's full probe.
+    const GsTable ct = G->committed, bt = G->batch;
+    for (uint32_t e = sub; e < cnt; e += 4 * LPF) {
+      unsigned long long v[4], c[4], b[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t ej = e + (uint32_t)j * LPF;
+        v[j] = 0;
+        if (ej < cnt) (void)gs_elem_lds(L, blen, h + ej * w0, &v[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t hs = gs_hash(v[j]);
+        c[j] = ld_slot(&ct.slots[hs & ct.mask]);
+        b[j] = ld_slot(&bt.slots[hs & bt.mask]);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        if (e + (uint32_t)j * LPF >= cnt) continue;
+        if (v[j] != 0 && (c[j] == v[j] || (c[j] == 0 && b[j] == v[j]))) continue;
+        gs_put(ct, bt, v[j]);
+      }
+    }
+  }
+  // general (mixed widths, d0..d3, non-minimal forms): the group's lane 0 walks the elements
+  // front to back, LPF to a round, and hands element k's offset to lane k; the lanes then read
+  // and insert their own.  The rounds are wave-uniform (the groups' counts differ).
+  uint32_t pos = h, remaining = general ? cnt : 0u;
+  while (__any(remaining > 0 && st == CE_OK)) {
+    const bool run = remaining > 0 && st == CE_OK;
+    const uint32_t todo = run ? (remaining < (uint32_t)LPF ? remaining : (uint32_t)LPF) : 0u;
+    uint32_t mine = 0xffffffffu;
+#pragma unroll 1
+    for (uint32_t k = 0; k < (uint32_t)LPF; k++) {
+      uint32_t w = 0;
+      unsigned long long v;
+      const bool step = k < todo && st == CE_OK;
+      if (step && sub == 0 && pos < blen) w = gs_elem_lds(L, blen, pos, &v);
+      w = (uint32_t)__shfl((int)w, (int)(grp * LPF));
+      if (step) {
+        if (w == 0) st = CE_ERR_DECODE;
+        else {
+          if (sub == k) mine = pos;
+          pos += w;
+        }
+      }
+    }
+    if (run && st == CE_OK) {
+      if (ins && mine != 0xffffffffu) {
+        unsigned long long v = 0;
+        (void)gs_elem_lds(L, blen, mine, &v);
+        gs_put(G->committed, G->batch, v);
+      }
+      remaining -= todo;
+    }
+  }
+  if (live && st != CE_OK && sub == 0) {
+    a.status[f] = st;
+    atomicAdd(&a.counters[3], 1u);
+    atomicMin(&a.counters[5], f);
+  }
+}
+
 __device__ const uint32_t kPolyOne[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 
 // ----------------------------------------------------------------------------------------
@@ -1486,7 +1648,10 @@ __device__ const uint32_t kPolyOne[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 // parameters loaded when this one starts (a whole iteration of latency) instead of in the decode
 // PN: the decode's op grammar (decode_fold's PN; a.batch in two planes); the open is the same
 // code.  Only k_open_fold_v3<false, true, true> is built: a PNCounter core takes no alternate.
-template <bool PAIR, bool EARLY, bool PN = false>
+// GS: the GSet grammar (decode_gset_lds, into the hash tables of a.gs) in place of decode_fold;
+// only k_open_fold_v3<false, true, false, true> is built.  Every GS difference is an `if
+// constexpr`: the other instantiations compile the code they always did.
+template <bool PAIR, bool EARLY, bool PN = false, bool GS = false>
 __global__ __launch_bounds__(64, 2)
 void k_open_fold_v3(DecodeArgs a) {
   constexpr int LPF = 16, F = 4, BPL = 4;
@@ -1502,6 +1667,7 @@ void k_open_fold_v3(DecodeArgs a) {
   FilePre2 nx = load_pre2(a, g * F + grp);
   const SupVers sup(a);
   DecState S{PN ? 51u : 38u, 0, 0, 0, 0, 0xffffffffu};
+  GsCounts gsc;
   AuthFails fails;
   // this lane's tree weight r^(4q), q = (sub + 15) & 15: X = r^(4 (q & 3)) in {1, r^4, r^8,
   // r^12}, Y = r^(16 (q >> 2)) in {1, r^16, r^32, r^48}, read from FileParams.rpow / PolyAux
@@ -1687,13 +1853,20 @@ void k_open_fold_v3(DecodeArgs a) {
     // 4) data-version check, decode from LDS, fold; the next iteration's parameters are loaded
     //    inside (their latency hides under the decode)
     if (CE_V3_PRIO) __builtin_amdgcn_s_setprio(CE_V3_PRIO);  // the decode's short dependent chains first
-    decode_fold<LPF, true, PN>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, S, [&] {
-      if (!EARLY) nx = load_pre2(a, (g + 1) * F + grp);
-    });
+    if constexpr (GS) {
+      decode_gset_lds<LPF>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, gsc, [&] {
+        if (!EARLY) nx = load_pre2(a, (g + 1) * F + grp);
+      });
+    } else {
+      decode_fold<LPF, true, PN>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, S, [&] {
+        if (!EARLY) nx = load_pre2(a, (g + 1) * F + grp);
+      });
+    }
     if (CE_V3_PRIO) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_wave_barrier();
   }
-  flush_pending<LPF>(a, sub, S.pslot, S.pbest);
+  if constexpr (GS) gsc.flush(a);
+  else flush_pending<LPF>(a, sub, S.pslot, S.pbest);
   fails.flush(a);
 }
 
@@ -1961,6 +2134,17 @@ hipError_t launch_open_fold_pn(hipStream_t s, const DecodeArgs& a, OpenLaunchLog
   const dim3 grid(log.grid(std::min<uint32_t>((a.n + 3) / 4, res), "open_v3_pn"));
   if (t0) hipExtLaunchKernelGGL((k_open_fold_v3<false, true, true>), grid, dim3(64), 0, s, t0, t1, 0u, a);
   else hipLaunchKernelGGL((k_open_fold_v3<false, true, true>), grid, dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_open_fold_gset(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log, hipEvent_t t0,
+                                 hipEvent_t t1) {
+  if (a.n == 0) return hipSuccess;
+  if (!a.aux || !a.gs) return hipErrorInvalidValue;  // the setup's PolyAux rows, the hash tables
+  static const uint32_t res = resident_blocks(k_open_fold_v3<false, true, false, true>, 64);
+  const dim3 grid(log.grid(std::min<uint32_t>((a.n + 3) / 4, res), "open_v3_gset"));
+  if (t0) hipExtLaunchKernelGGL((k_open_fold_v3<false, true, false, true>), grid, dim3(64), 0, s, t0, t1, 0u, a);
+  else hipLaunchKernelGGL((k_open_fold_v3<false, true, false, true>), grid, dim3(64), 0, s, a);
   return hipGetLastError();
 }
 

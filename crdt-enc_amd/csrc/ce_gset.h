@@ -1,0 +1,69 @@
+// ce_gset.h -- GSet<u64> (crdts 7: struct GSet<T> { value: BTreeSet<T> }, Op = T): the device
+// hash set and its kernels' launch interface (ce_gset.hip), driven by ce_gset_host.cpp.
+//
+// Table: open addressing over u64 keys, linear probing, capacity a power of two.  An empty slot
+// holds 0; the member 0 is held out of band (meta[kGsZero]).  A probe that finds its key does no
+// atomic; a probe that reaches an empty slot reserves one unit of the live count, then claims the
+// slot with a 64-bit CAS.  The count never passes `limit` (half the capacity), so a probe always
+// ends at the key or at an empty slot; a reservation that would pass it raises meta[kGsOverflow]
+// instead, and the host grows the table and runs the launch again (inserts are idempotent).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ce_kernels.h"
+
+namespace ce {
+
+static constexpr int kGsCount = 0;     // claimed slots (the member 0 not counted)
+static constexpr int kGsZero = 1;      // the member 0 is in the set
+static constexpr int kGsOverflow = 2;  // an insert was refused at the load bound
+static constexpr int kGsMetaWords = 4;
+
+struct GsTable {
+  unsigned long long* slots;  // [mask + 1]
+  uint32_t mask;
+  uint32_t limit;             // claims allowed: (mask + 1) / 2
+  uint32_t* meta;             // kGsMetaWords words
+};
+
+struct GsDecodeArgs {
+  const uint8_t* pt;          // plaintext blob (FileParams.out_off / len)
+  const FileParams* params;
+  int32_t* status;
+  uint32_t n;
+  const uint8_t* supported;   // n_supported * 16 bytes
+  uint32_t n_supported;
+  const uint8_t* apply;       // 1 = insert this file's members (version gate)
+  const uint8_t* only;        // null, or per file: decode only files with only[i] != 0
+  int large_only;             // only files of more than one page (the fused open took the others)
+  GsTable committed;          // probed read-only
+  GsTable batch;              // members absent from `committed` are claimed here
+  uint32_t* paths;            // [0] files of one element width, [1] files of the general path
+};
+
+// what the fused open's GSet grammar (ce_fused.hip k_open_fold_v3<false, true, false, true>) reads
+// through DecodeArgs.gs (device memory): the two tables, and the launch's file counts
+// paths[0] uniform, [1] general (shared with k_decode_gset), [2] files decoded in the open
+struct GsFused {
+  GsTable committed, batch;
+  uint32_t* paths;
+};
+
+// one wave per file: data version, array header, the uniform-width or the general path; statuses
+// CE_ERR_PT_LEN / CE_ERR_PT_VERSION / CE_ERR_DECODE into a.status
+hipError_t launch_decode_gset(hipStream_t s, const GsDecodeArgs& a, uint32_t grid_waves);
+// keys[0..n) into t (a state file's members, local ops)
+hipError_t launch_gs_insert(hipStream_t s, GsTable t, const unsigned long long* keys, uint32_t n);
+// every member of src into dst (the batch's commit, and a growth's rehash)
+hipError_t launch_gs_move(hipStream_t s, GsTable src, GsTable dst);
+// the live members of t, in no order, into out[0..*n_out) (*n_out zero before the launch)
+hipError_t launch_gs_collect(hipStream_t s, GsTable t, unsigned long long* out, uint32_t* n_out);
+// the serializer over the sorted members v[0..n): w[i] = element i's encoded length (1, 2, 3, 5
+// or 9); then, with off = the exclusive scan of w, element i written at out[off[i]] and the clear
+// length head_len + off[n - 1] + w[n - 1] at clear_len_at (the seal's offs[1])
+hipError_t launch_gs_widths(hipStream_t s, const unsigned long long* v, uint32_t n, uint32_t* w);
+hipError_t launch_gs_write(hipStream_t s, const unsigned long long* v, const uint32_t* off, uint32_t n, uint8_t* out,
+                           unsigned long long* clear_len_at, uint64_t head_len);
+
+}  // namespace ce

@@ -1,0 +1,238 @@
+// ce_gset.hip -- GSet<u64> on the device (gfx950): the u64 hash set (ce_gset.h) and the
+// wave-per-file decode of an op file's Vec<u64> from plaintext in HBM.
+//
+// Element grammar (oracle/crdts.py _u64 over rmp's integer forms): positive fixint, cc / cd / ce /
+// cf, and d0..d3 with a non-negative value; every other marker, and an element cut short by the
+// end of the file, is CE_ERR_DECODE.  Bytes after the array are ignored.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ce_gset.h"
+#include "ce_gset_device.h"
+
+namespace ce {
+namespace {
+
+constexpr int kWaves = 4;  // waves per block
+
+// the element at body[p]: its encoded length (0: invalid or cut short) and value
+__device__ uint32_t gs_elem(const uint8_t* body, uint32_t blen, uint32_t p, unsigned long long* out) {
+  if (p >= blen) return 0;
+  const uint32_t m = body[p];
+  if (m <= 0x7f) {
+    *out = m;
+    return 1;
+  }
+  if (m < 0xcc || m > 0xd3) return 0;
+  const bool sgn = m >= 0xd0;
+  const uint32_t w = 1u << ((m - 0xcc) & 3);
+  if (blen - p - 1 < w) return 0;
+  unsigned long long x = 0;
+  for (uint32_t k = 0; k < w; k++) x = (x << 8) | body[p + 1 + k];
+  if (sgn && ((x >> (8 * w - 1)) & 1)) return 0;  // a negative integer
+  *out = x;
+  return 1 + w;
+}
+
+__device__ void decode_gset_file(const GsDecodeArgs& a, uint32_t f, uint32_t lane) {
+  const FileParams* Pp = a.params + f;
+  const uint8_t* pt = a.pt + Pp->out_off;
+  const uint32_t len = Pp->len;
+  int32_t st = CE_OK;
+  // clear text = VersionBytes(data_version, msgpack(Vec<u64>)) (crdt-enc/src/lib.rs:504-507)
+  if (len < 16) st = CE_ERR_PT_LEN;
+  else {
+    const uint4 dv = *reinterpret_cast<const uint4*>(pt);
+    bool found = false;
+    for (uint32_t s = 0; s < a.n_supported; s++) {
+      const uint4 sv = *reinterpret_cast<const uint4*>(a.supported + 16 * s);
+      found |= dv.x == sv.x && dv.y == sv.y && dv.z == sv.z && dv.w == sv.w;
+    }
+    if (!found) st = CE_ERR_PT_VERSION;
+  }
+  const bool ins = st == CE_OK && a.apply[f];
+  auto put = [&](unsigned long long v) { gs_put(a.committed, a.batch, v); };
+  if (st == CE_OK) {
+    const uint8_t* body = pt + 16;
+    const uint32_t blen = len - 16;
+    uint32_t cnt = 0, h = 0;
+    if (blen == 0) st = CE_ERR_DECODE;
+    else {
+      const uint32_t m = body[0];
+      if ((m & 0xf0) == 0x90) { cnt = m & 15; h = 1; }
+      else if (m == 0xdc && blen >= 3) { cnt = (uint32_t)body[1] << 8 | body[2]; h = 3; }
+      else if (m == 0xdd && blen >= 5) {
+        cnt = (uint32_t)body[1] << 24 | (uint32_t)body[2] << 16 | (uint32_t)body[3] << 8 | body[4];
+        h = 5;
+      } else st = CE_ERR_DECODE;
+      if (st == CE_OK && cnt > blen - h) st = CE_ERR_DECODE;  // each element takes >= 1 byte
+    }
+    if (st == CE_OK) {
+      // uniform width: every element has the first one's marker (any positive fixint for a
+      // fixint), and count x width fits.  Lane L checks the markers of elements L, L + 64, ...
+      uint32_t w0 = 0, mk = 0;
+      if (cnt > 0) {
+        mk = body[h];
+        w0 = mk <= 0x7f ? 1u : (mk >= 0xcc && mk <= 0xcf) ? 1u + (1u << (mk - 0xcc)) : 0u;
+        if (w0 && (unsigned long long)cnt * w0 > blen - h) w0 = 0;
+      }
+      bool ok = w0 != 0;
+      if (w0)
+        for (uint32_t e = lane; e < cnt && ok; e += 64) {
+          const uint32_t m = body[h + e * w0];
+          ok = w0 == 1 ? m <= 0x7f : m == mk;
+        }
+      const bool uniform = cnt == 0 || __ballot(ok) == ~0ull;
+      if (uniform) {
+        if (lane == 0) atomicAdd(&a.paths[0], 1u);
+        if (ins) {
+          for (uint32_t e = lane; e < cnt; e += 64) {
+            unsigned long long v = 0;
+            (void)gs_elem(body, blen, h + e * w0, &v);
+            put(v);
+          }
+        }
+      } else {
+        // general: lane 0 walks the elements front to back, 64 to a round, and hands element k's
+        // position to lane k; the lanes then read and insert their own.  Members of a file that
+        // fails further on land in the batch table only, which a rejected batch clears.
+        if (lane == 0) atomicAdd(&a.paths[1], 1u);
+        uint32_t pos = h, remaining = cnt;
+        while (remaining > 0 && st == CE_OK) {
+          const uint32_t todo = remaining < 64 ? remaining : 64;
+          uint32_t mine = 0xffffffffu;
+          for (uint32_t k = 0; k < todo; k++) {
+            uint32_t w = 0;
+            unsigned long long v;
+            if (lane == 0) w = gs_elem(body, blen, pos, &v);
+            w = (uint32_t)__shfl((int)w, 0);
+            if (w == 0) { st = CE_ERR_DECODE; break; }
+            if (lane == k) mine = pos;
+            pos += w;
+          }
+          if (st != CE_OK) break;
+          if (ins && mine != 0xffffffffu) {
+            unsigned long long v = 0;
+            (void)gs_elem(body, blen, mine, &v);
+            put(v);
+          }
+          remaining -= todo;
+        }
+      }
+    }
+  }
+  if (st != CE_OK && lane == 0) a.status[f] = st;
+}
+
+__global__ __launch_bounds__(256) void k_decode_gset(GsDecodeArgs a) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t stride = gridDim.x * kWaves;
+  for (uint32_t f = __builtin_amdgcn_readfirstlane(blockIdx.x * kWaves + (threadIdx.x >> 6)); f < a.n; f += stride) {
+    if (a.only && !a.only[f]) continue;
+    if (a.large_only && a.params[f].len <= kSmallMax) continue;  // (the fused open decoded those)
+    if (a.status[f] != CE_OK) continue;
+    decode_gset_file(a, f, lane);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_gs_insert(GsTable t, const unsigned long long* keys, uint32_t n) {
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) gs_insert(t, keys[i]);
+}
+
+__global__ __launch_bounds__(256) void k_gs_move(GsTable src, GsTable dst) {
+  if (blockIdx.x == 0 && threadIdx.x == 0 && src.meta[kGsZero]) gs_insert(dst, 0);
+  const uint32_t cap = src.mask + 1;
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < cap; i += gridDim.x * 256) {
+    const unsigned long long v = src.slots[i];
+    if (v) gs_insert(dst, v);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_gs_collect(GsTable t, unsigned long long* out, uint32_t* n_out) {
+  if (blockIdx.x == 0 && threadIdx.x == 0 && t.meta[kGsZero]) out[atomicAdd(n_out, 1u)] = 0;
+  const uint32_t cap = t.mask + 1;
+  // one atomicAdd per wave and round: the wave's live slots take consecutive places
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < cap; i += gridDim.x * 256) {
+    const unsigned long long v = t.slots[i];
+    const unsigned long long m = __ballot(v != 0);
+    if (m == 0) continue;
+    const int leader = __builtin_ctzll(m);
+    uint32_t base = 0;
+    if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(n_out, (uint32_t)__popcll(m));
+    base = (uint32_t)__shfl((int)base, leader);
+    if (v) out[base + (uint32_t)__popcll(m & ((1ull << (threadIdx.x & 63)) - 1))] = v;
+  }
+}
+
+// the serializer: an element's encoded length (its smallest unsigned form), and the writer
+__device__ __forceinline__ uint32_t gs_width(unsigned long long v) {
+  return v <= 0x7f ? 1u : v <= 0xff ? 2u : v <= 0xffff ? 3u : v <= 0xffffffffull ? 5u : 9u;
+}
+
+__global__ __launch_bounds__(256) void k_gs_widths(const unsigned long long* v, uint32_t n, uint32_t* w) {
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) w[i] = gs_width(v[i]);
+}
+
+// element i at out[off[i]]; the last element's thread writes the clear length (head_len + the
+// elements' bytes) where the seal reads it
+__global__ __launch_bounds__(256) void k_gs_write(const unsigned long long* v, const uint32_t* off, uint32_t n,
+                                                  uint8_t* out, unsigned long long* clear_len_at,
+                                                  unsigned long long head_len) {
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const unsigned long long x = v[i];
+    const uint32_t w = gs_width(x);
+    uint8_t* p = out + off[i];
+    if (w == 1) p[0] = (uint8_t)x;
+    else {
+      p[0] = (uint8_t)(w == 2 ? 0xcc : w == 3 ? 0xcd : w == 5 ? 0xce : 0xcf);
+      for (uint32_t k = 1; k < w; k++) p[k] = (uint8_t)(x >> (8 * (w - 1 - k)));
+    }
+    if (i == n - 1) *clear_len_at = head_len + off[i] + w;
+  }
+}
+
+uint32_t blocks_for(uint32_t n) {
+  const uint32_t b = (n + 255) / 256;
+  return b < 1 ? 1 : (b > 4096 ? 4096 : b);
+}
+
+}  // namespace
+
+hipError_t launch_decode_gset(hipStream_t s, const GsDecodeArgs& a, uint32_t grid_waves) {
+  if (a.n == 0) return hipSuccess;
+  const uint32_t blocks = (grid_waves + kWaves - 1) / kWaves;
+  hipLaunchKernelGGL(k_decode_gset, dim3(blocks < 1 ? 1 : blocks), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_gs_insert(hipStream_t s, GsTable t, const unsigned long long* keys, uint32_t n) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gs_insert, dim3(blocks_for(n)), dim3(256), 0, s, t, keys, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_gs_move(hipStream_t s, GsTable src, GsTable dst) {
+  hipLaunchKernelGGL(k_gs_move, dim3(blocks_for(src.mask + 1)), dim3(256), 0, s, src, dst);
+  return hipGetLastError();
+}
+
+hipError_t launch_gs_widths(hipStream_t s, const unsigned long long* v, uint32_t n, uint32_t* w) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gs_widths, dim3(blocks_for(n)), dim3(256), 0, s, v, n, w);
+  return hipGetLastError();
+}
+
+hipError_t launch_gs_write(hipStream_t s, const unsigned long long* v, const uint32_t* off, uint32_t n, uint8_t* out,
+                           unsigned long long* clear_len_at, uint64_t head_len) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gs_write, dim3(blocks_for(n)), dim3(256), 0, s, v, off, n, out, clear_len_at,
+                     (unsigned long long)head_len);
+  return hipGetLastError();
+}
+
+hipError_t launch_gs_collect(hipStream_t s, GsTable t, unsigned long long* out, uint32_t* n_out) {
+  hipLaunchKernelGGL(k_gs_collect, dim3(blocks_for(t.mask + 1)), dim3(256), 0, s, t, out, n_out);
+  return hipGetLastError();
+}
+
+}  // namespace ce

@@ -1,0 +1,552 @@
+// ce_gset_host.cpp -- Core<GSet<u64>> (CE_STATE_GSET): the host side of the device hash set
+// (ce_gset.h).  Same contracts as the VClock / GCounter paths in ce_core.cpp.
+//
+// All-or-nothing (lib.rs:497-514): single-page files are opened, checked and decoded in the fused
+// open (ce_fused.hip k_open_fold_v3's GS form, plaintext in LDS); larger files, host-parse
+// envelopes, multi-key retries and a refold after the batch table grew go through HBM and
+// k_decode_gset.  Both insert the gated files' members into the BATCH table, probing the committed
+// table read-only (members already known claim nothing).  The host then reads the statuses: a
+// failure clears the batch table and the committed set is untouched; otherwise k_gs_move commits
+// the batch table's members.  Growth: a launch that raised the overflow flag is run again after
+// the host rehashed the table into twice the capacity (inserts are idempotent).
+#include <algorithm>
+#include <cstring>
+
+#include "ce_core.h"
+#include "ce_dotset.h"
+#include "ce_dotset_io.h"
+#include "ce_gset.h"
+
+namespace ce {
+
+struct GsState {
+  DevBuf slots, bslots;  // committed / batch table
+  DevBuf meta;           // u32 words: committed [0,4) | batch [4,8) | rehash [8,12) | paths [12,15) | collect count [15]
+  uint32_t cap = 0, bcap = 0;
+  bool batch_dirty = false;
+  DevBuf col, sorted, vals, sort_tmp, scan_tmp, only;
+  DevBuf fused;     // GsFused: what the fused open reads through DecodeArgs.gs
+  GsFused h_fused;  // its host copy (lives through the upload)
+};
+
+void gs_free(GsState* g) { delete g; }
+
+namespace {
+
+constexpr uint32_t kMetaWords = 16;
+constexpr uint32_t kMinCap = 16;
+
+uint32_t pow2_at_least(uint64_t v) {
+  uint32_t p = kMinCap;
+  while (p < v && p < (1u << 31)) p <<= 1;
+  return p;
+}
+
+GsTable committed(const GsState* g) {
+  return GsTable{g->slots.as<unsigned long long>(), g->cap - 1, g->cap / 2, g->meta.as<uint32_t>()};
+}
+GsTable batch(const GsState* g) {
+  return GsTable{g->bslots.as<unsigned long long>(), g->bcap - 1, g->bcap / 2, g->meta.as<uint32_t>() + 4};
+}
+
+int read_meta(ce_core* c, uint32_t* hm) {
+  hipError_t e;
+  if ((e = hipMemcpyAsync(hm, c->gs->meta.p, kMetaWords * 4, hipMemcpyDeviceToHost, c->ctx->stream)) ||
+      (e = stream_wait(c->ctx->stream)))
+    return c->ctx->hip_fail(e, "gset meta");
+  return CE_OK;
+}
+
+// rehash one of the tables into new_cap slots (its count is rebuilt by the claims)
+int rehash(ce_core* c, bool is_batch, uint32_t new_cap) {
+  GsState* g = c->gs;
+  hipStream_t s = c->ctx->stream;
+  DevBuf nb;
+  hipError_t e;
+  uint32_t* meta = g->meta.as<uint32_t>();
+  if ((e = nb.reserve((size_t)new_cap * 8)) || (e = hipMemsetAsync(nb.p, 0, (size_t)new_cap * 8, s)) ||
+      (e = hipMemsetAsync(meta + 8, 0, 16, s)))
+    return c->ctx->hip_fail(e, "gset grow");
+  const GsTable src = is_batch ? batch(g) : committed(g);
+  const GsTable dst{nb.as<unsigned long long>(), new_cap - 1, new_cap / 2, meta + 8};
+  if ((e = launch_gs_move(s, src, dst)) ||
+      (e = hipMemcpyAsync(src.meta, meta + 8, 16, hipMemcpyDeviceToDevice, s)) || (e = stream_wait(s)))
+    return c->ctx->hip_fail(e, "gset grow");
+  if (is_batch) {
+    g->bslots = std::move(nb);
+    g->bcap = new_cap;
+  } else {
+    g->slots = std::move(nb);
+    g->cap = new_cap;
+  }
+  c->path_counts[is_batch ? "gset_batch_grows" : "gset_grows"]++;
+  return CE_OK;
+}
+
+// room in the committed table for `extra` more claims (count: its claims now)
+int ensure_committed(ce_core* c, uint64_t count, uint64_t extra) {
+  GsState* g = c->gs;
+  if (count + extra <= g->cap / 2) return CE_OK;
+  if (count + extra > (1ull << 30)) return c->ctx->fail(CE_ERR_INVALID_ARG, "set too large for the table");
+  return rehash(c, false, pow2_at_least(2 * (count + extra)));
+}
+
+int clear_batch(ce_core* c) {
+  GsState* g = c->gs;
+  hipError_t e;
+  if ((e = hipMemsetAsync(g->bslots.p, 0, (size_t)g->bcap * 8, c->ctx->stream)) ||
+      (e = hipMemsetAsync(g->meta.as<uint32_t>() + 4, 0, 16, c->ctx->stream)))
+    return c->ctx->hip_fail(e, "gset batch clear");
+  g->batch_dirty = false;
+  return CE_OK;
+}
+
+// decode the files of `only` (null: all; large_only: those of more than one page) from their
+// plaintext in HBM into the batch table, growing it until the pass fits
+int decode_pass(ce_core* c, uint32_t n, const uint8_t* only, bool large_only = false) {
+  ce_ctx* ctx = c->ctx;
+  GsState* g = c->gs;
+  hipError_t e;
+  for (int round = 0;; round++) {
+    GsDecodeArgs a{};
+    a.pt = ctx->out.as<uint8_t>();
+    a.params = ctx->params.as<FileParams>();
+    a.status = ctx->status.as<int32_t>();
+    a.n = n;
+    a.supported = c->d_supported.as<uint8_t>();
+    a.n_supported = (uint32_t)c->supported.size();
+    a.apply = ctx->apply.as<uint8_t>();
+    a.only = only;
+    a.large_only = large_only ? 1 : 0;
+    a.committed = committed(g);
+    a.batch = batch(g);
+    a.paths = g->meta.as<uint32_t>() + 12;
+    if ((e = hipMemsetAsync(a.paths, 0, 12, ctx->stream))) return ctx->hip_fail(e, "gset decode");
+    const int t = ctx->tbegin("decode_gset");
+    if ((e = launch_decode_gset(ctx->stream, a, grid_waves_for(n)))) return ctx->hip_fail(e, "gset decode");
+    ctx->tend(t);
+    g->batch_dirty = true;
+    uint32_t hm[kMetaWords];
+    int rc = read_meta(c, hm);
+    if (rc) return rc;
+    if (!hm[4 + kGsOverflow]) {
+      c->path_counts["gset_uniform_files"] += hm[12];
+      c->path_counts["gset_general_files"] += hm[13];
+      return CE_OK;
+    }
+    if (round > 32 || g->bcap >= (1u << 31)) return ctx->fail(CE_ERR_DEVICE, "batch table did not converge");
+    if ((e = hipMemsetAsync(g->meta.as<uint32_t>() + 4 + kGsOverflow, 0, 4, ctx->stream)))
+      return ctx->hip_fail(e, "gset decode");
+    if ((rc = rehash(c, true, g->bcap * 2))) return rc;
+  }
+}
+
+int download_status(ce_core* c, uint32_t n, std::vector<int32_t>* st) {
+  st->resize(n);
+  hipError_t e;
+  if ((e = hipMemcpyAsync(st->data(), c->ctx->status.p, n * 4ull, hipMemcpyDeviceToHost, c->ctx->stream)) ||
+      (e = stream_wait(c->ctx->stream)))
+    return c->ctx->hip_fail(e, "status");
+  return CE_OK;
+}
+
+// the batch table's members into the committed table
+int commit_batch(ce_core* c) {
+  GsState* g = c->gs;
+  uint32_t hm[kMetaWords];
+  int rc = read_meta(c, hm);
+  if (rc) return rc;
+  if (hm[4 + kGsCount] == 0 && hm[4 + kGsZero] == 0) return clear_batch(c);
+  if ((rc = ensure_committed(c, hm[kGsCount], hm[4 + kGsCount]))) return rc;
+  hipError_t e;
+  const int t = c->ctx->tbegin("gset_commit");
+  if ((e = launch_gs_move(c->ctx->stream, batch(g), committed(g)))) return c->ctx->hip_fail(e, "gset commit");
+  c->ctx->tend(t);
+  return clear_batch(c);
+}
+
+bool read_members(Rd& r, std::vector<uint64_t>* out) {
+  uint64_t cnt;
+  if (!rd_array_hdr(r, &cnt) || cnt > r.n - r.i) return false;  // each element takes >= 1 byte
+  out->reserve(out->size() + cnt);
+  for (uint64_t k = 0; k < cnt; k++) {
+    uint64_t v;
+    if (!rd_u64(r, &v)) return false;
+    out->push_back(v);
+  }
+  return true;
+}
+
+}  // namespace
+
+bool parse_gset_ops(const uint8_t* p, size_t n, std::vector<uint64_t>* out) {
+  Rd r{p, n, 0};
+  return read_members(r, out);
+}
+
+bool read_gset_state(Rd& r, std::vector<uint64_t>* out) {
+  return read_struct(r, {"value"}, [&](int, Rd& q) { return read_members(q, out); });
+}
+
+void write_gset_state(Wr* w, const std::vector<uint64_t>& sorted_members) {
+  w->map(1);
+  w->str("value");
+  w->arr(sorted_members.size());
+  for (uint64_t v : sorted_members) w->uint(v);
+}
+
+int gs_init(ce_core* c) {
+  GsState* g = c->gs = new GsState();
+  uint32_t cap = 1u << 16;
+  if (const char* e = getenv("CE_GSET_CAP")) cap = pow2_at_least((uint64_t)std::max(1l, atol(e)));
+  g->cap = g->bcap = cap;
+  hipError_t e;
+  hipStream_t s = c->ctx->stream;
+  if ((e = g->slots.reserve((size_t)cap * 8)) || (e = g->bslots.reserve((size_t)cap * 8)) ||
+      (e = g->meta.reserve(kMetaWords * 4)) || (e = hipMemsetAsync(g->slots.p, 0, (size_t)cap * 8, s)) ||
+      (e = hipMemsetAsync(g->bslots.p, 0, (size_t)cap * 8, s)) ||
+      (e = hipMemsetAsync(g->meta.p, 0, kMetaWords * 4, s)) || (e = stream_wait(s)))
+    return c->ctx->hip_fail(e, "gset init");
+  return CE_OK;
+}
+
+int gs_reset(ce_core* c) {
+  GsState* g = c->gs;
+  hipError_t e;
+  if ((e = hipMemsetAsync(g->slots.p, 0, (size_t)g->cap * 8, c->ctx->stream)) ||
+      (e = hipMemsetAsync(g->meta.p, 0, kMetaWords * 4, c->ctx->stream)))
+    return c->ctx->hip_fail(e, "gset reset");
+  return clear_batch(c);
+}
+
+int gs_settle(ce_core* c) {
+  hipError_t e = stream_wait(c->ctx->stream);
+  return e ? c->ctx->hip_fail(e, "settle") : CE_OK;
+}
+
+int gs_insert_members(ce_core* c, const std::vector<uint64_t>& members) {
+  if (members.empty()) return CE_OK;
+  if (members.size() > (1u << 30)) return c->ctx->fail(CE_ERR_INVALID_ARG, "too many members");
+  GsState* g = c->gs;
+  uint32_t hm[kMetaWords];
+  int rc = read_meta(c, hm);
+  if (rc || (rc = ensure_committed(c, hm[kGsCount], members.size()))) return rc;
+  hipError_t e;
+  hipStream_t s = c->ctx->stream;
+  if ((e = g->col.reserve(members.size() * 8 + 64)) ||
+      (e = hipMemcpyAsync(g->col.p, members.data(), members.size() * 8, hipMemcpyHostToDevice, s)) ||
+      (e = launch_gs_insert(s, committed(g), g->col.as<unsigned long long>(), (uint32_t)members.size())) ||
+      (e = stream_wait(s)))  // (the upload reads the caller's vector)
+    return c->ctx->hip_fail(e, "gset insert");
+  return CE_OK;
+}
+
+// the set in BTreeSet order in g->sorted (device): the live slots collected, then the radix sort
+// (ce_ser_sort.hip's generic u64 key mode); *n_out = the member count
+static int collect_sorted(ce_core* c, uint32_t* n_members) {
+  GsState* g = c->gs;
+  hipStream_t s = c->ctx->stream;
+  uint32_t hm[kMetaWords];
+  int rc = read_meta(c, hm);
+  if (rc) return rc;
+  const uint32_t n = *n_members = hm[kGsCount] + (hm[kGsZero] ? 1u : 0u);
+  if (n == 0) return CE_OK;
+  hipError_t e;
+  uint32_t* n_out = g->meta.as<uint32_t>() + 15;
+  size_t tb = 0;
+  if ((e = g->col.reserve((size_t)n * 8 + 64)) || (e = g->sorted.reserve((size_t)n * 8 + 64)) ||
+      (e = g->vals.reserve((size_t)n * 8 + 64)) ||
+      (e = sort_pairs_u64(nullptr, tb, nullptr, nullptr, nullptr, nullptr, n, 64, s)) ||
+      (e = g->sort_tmp.reserve(tb + 256)))
+    return c->ctx->hip_fail(e, "gset collect");
+  tb = g->sort_tmp.cap;
+  uint32_t* vin = g->vals.as<uint32_t>();
+  const int t = c->ctx->tbegin("gset_sort");  // (the collect and the radix sort's passes)
+  if ((e = hipMemsetAsync(n_out, 0, 4, s)) ||
+      (e = launch_gs_collect(s, committed(g), g->col.as<unsigned long long>(), n_out)) ||
+      (e = sort_pairs_u64(g->sort_tmp.p, tb, g->col.as<unsigned long long>(), g->sorted.as<unsigned long long>(),
+                          vin, vin + n, n, 64, s)))
+    return c->ctx->hip_fail(e, "gset collect");
+  c->ctx->tend(t);
+  return CE_OK;
+}
+
+int gs_members_sorted(ce_core* c, std::vector<uint64_t>* out) {
+  uint32_t n = 0;
+  int rc = collect_sorted(c, &n);
+  if (rc) return rc;
+  out->resize(n);
+  hipError_t e;
+  if (n && ((e = hipMemcpyAsync(out->data(), c->gs->sorted.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->ctx->stream)) ||
+            (e = stream_wait(c->ctx->stream))))
+    return c->ctx->hip_fail(e, "gset collect");
+  return CE_OK;
+}
+
+namespace {
+
+// The device writer.  head: the clear text up to and including a5"state" (the host's part: the
+// optional data version and next_op_versions).  Into ctx->blob: head, 81 a5"value", the array
+// header and the members ascending, each in its smallest form; at A = *args_at (past the clear
+// text's bound) the seal's small arguments [offs(2) | out_offs(1) | nonce (24 B) | outer version
+// (16 B)], offs[1] = the clear length, written by the writer's last thread.  Nothing is waited for.
+int write_device(ce_core* c, std::vector<uint8_t> head, const uint8_t* nonce, const uint8_t* outer,
+                 uint64_t* args_at, uint64_t* bound) {
+  ce_ctx* ctx = c->ctx;
+  GsState* g = c->gs;
+  hipStream_t s = ctx->stream;
+  uint32_t n = 0;
+  int rc = collect_sorted(c, &n);
+  if (rc) return rc;
+  if (9ull * n >= (1ull << 32)) return ctx->fail(CE_ERR_INVALID_ARG, "set too large for 32-bit element offsets");
+  Wr w;
+  w.b.swap(head);
+  w.map(1);
+  w.str("value");
+  w.arr(n);
+  const uint64_t head_len = w.b.size();
+  const uint64_t U = *bound = head_len + 9ull * n;
+  const uint64_t A = *args_at = (U + 255) & ~255ull;
+  hipError_t e;
+  if ((e = ctx->blob.reserve(A + 128)) || (e = ctx->h_stage.reserve(head_len + 64 + 256)) ||
+      (e = g->vals.reserve((size_t)n * 8 + 64)))
+    return ctx->hip_fail(e, "gset writer");
+  uint8_t* hs = ctx->h_stage.as<uint8_t>();
+  uint8_t* db = ctx->blob.as<uint8_t>();
+  const uint64_t args[3] = {0, head_len, 0};  // offs[1]: an empty set's clear length
+  std::memcpy(hs, w.b.data(), head_len);
+  uint8_t* ha = hs + ((head_len + 7) & ~7ull);
+  std::memset(ha, 0, 64);
+  std::memcpy(ha, args, 24);
+  if (nonce) std::memcpy(ha + 24, nonce, 24);
+  if (outer) std::memcpy(ha + 48, outer, 16);
+  if ((e = hipMemcpyAsync(db, hs, head_len, hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(db + A, ha, 64, hipMemcpyHostToDevice, s)))
+    return ctx->hip_fail(e, "gset writer");
+  c->path_counts["gset_device_writes"]++;
+  if (n == 0) return CE_OK;  // (the head is the whole state)
+  const unsigned long long* sorted = g->sorted.as<unsigned long long>();
+  uint32_t* wid = g->vals.as<uint32_t>();
+  uint32_t* off = wid + n;
+  size_t tb = 0;
+  if ((e = ds_excl_sum_u32(nullptr, tb, wid, off, n, s)) || (e = g->scan_tmp.reserve(tb + 256)))
+    return ctx->hip_fail(e, "gset writer");
+  tb = g->scan_tmp.cap;
+  const int t = ctx->tbegin("gset_write");
+  if ((e = launch_gs_widths(s, sorted, n, wid)) || (e = ds_excl_sum_u32(g->scan_tmp.p, tb, wid, off, n, s)) ||
+      (e = launch_gs_write(s, sorted, off, n, db + head_len, reinterpret_cast<unsigned long long*>(db + A + 8),
+                           head_len)))
+    return ctx->hip_fail(e, "gset writer");
+  ctx->tend(t);
+  return CE_OK;
+}
+
+}  // namespace
+
+int gs_serialize_device(ce_core* c, std::vector<uint8_t> head, std::vector<uint8_t>* out) {
+  ce_ctx* ctx = c->ctx;
+  uint64_t A = 0, U = 0, clear_len = 0;
+  int rc = write_device(c, std::move(head), nullptr, nullptr, &A, &U);
+  if (rc) return rc;
+  const uint8_t* db = ctx->blob.as<uint8_t>();
+  hipError_t e;
+  if ((e = hipMemcpyAsync(&clear_len, db + A + 8, 8, hipMemcpyDeviceToHost, ctx->stream)) ||
+      (e = stream_wait(ctx->stream)))
+    return ctx->hip_fail(e, "gset state bytes");
+  if (clear_len > U) return ctx->fail(CE_ERR_DEVICE, "serialized state past its bound");
+  out->resize(clear_len);
+  if (clear_len && ((e = hipMemcpyAsync(out->data(), db, clear_len, hipMemcpyDeviceToHost, ctx->stream)) ||
+                    (e = stream_wait(ctx->stream))))
+    return ctx->hip_fail(e, "gset state bytes");
+  return CE_OK;
+}
+
+int gs_compact_device(ce_core* c, std::vector<uint8_t> head, const uint8_t* outer, const uint8_t* nonce,
+                      const KeyRef& key, std::vector<uint8_t>* file) {
+  ce_ctx* ctx = c->ctx;
+  if (int32_t ks = key_status(key)) return ctx->fail(ks, "key rejected");
+  uint8_t nb[24];
+  if (nonce) std::memcpy(nb, nonce, 24);
+  else os_random(nb, 24);
+  uint64_t A = 0, U = 0, clear_len = 0;
+  int rc = write_device(c, std::move(head), nb, outer, &A, &U);
+  if (rc) return rc;
+  hipError_t e;
+  if ((e = ctx->out.reserve(16 + sealed_len(U) + 64))) return ctx->hip_fail(e, "gset compact");
+  uint8_t* db = ctx->blob.as<uint8_t>();
+  if ((rc = device_seal(ctx, db, reinterpret_cast<const uint64_t*>(db + A), 1, U, db + A + 48, db + A + 24,
+                        ctx->out.as<uint8_t>(), reinterpret_cast<const uint64_t*>(db + A + 16), key)))
+    return rc;
+  if ((e = hipMemcpyAsync(&clear_len, db + A + 8, 8, hipMemcpyDeviceToHost, ctx->stream)) ||
+      (e = stream_wait(ctx->stream)))
+    return ctx->hip_fail(e, "gset compact");
+  if (clear_len > U) return ctx->fail(CE_ERR_DEVICE, "serialized state past its bound");
+  file->resize(16 + sealed_len(clear_len));
+  if ((e = hipMemcpyAsync(file->data(), ctx->out.p, file->size(), hipMemcpyDeviceToHost, ctx->stream)) ||
+      (e = stream_wait(ctx->stream)))
+    return ctx->hip_fail(e, "gset compact");
+  return CE_OK;
+}
+
+int gs_ingest_ops(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n,
+                  uint64_t blob_len, const uint8_t* actors, uint32_t m, const uint32_t* d_fa,
+                  const uint64_t* d_fv, int32_t* status_out) {
+  ce_ctx* ctx = c->ctx;
+  GsState* g = c->gs;
+  hipError_t e;
+  int rc;
+  // writers get slots first (the gate is keyed by them)
+  std::vector<uint32_t> wslot(m);
+  const uint64_t gen0 = c->table_gen;
+  for (uint32_t a = 0; a < m; a++) {
+    Uuid u;
+    std::memcpy(u.data(), actors + 16ull * a, 16);
+    if ((rc = insert_actor(c, u, &wslot[a]))) return rc;
+  }
+  if (c->table_gen != gen0) refresh_slots(c, actors, m, &wslot);
+  if ((rc = table_upload(c)) || (rc = ensure_supported(c))) return rc;
+  if ((e = ctx->out.reserve(blob_len + 16ull * n + 128)) || (e = ctx->status.reserve(n * 4ull + 64)) ||
+      (e = ctx->apply.reserve(n + 64)) || (e = g->only.reserve(n + 64)))
+    return ctx->hip_fail(e, "ingest reserve");
+  if (g->batch_dirty && (rc = clear_batch(c))) return rc;
+  // 1) the version gate (lib.rs:519-538) on the host: it needs no plaintext
+  std::vector<uint32_t> fa(n);
+  std::vector<uint64_t> fv(n), expect(m);
+  std::vector<uint8_t> ap(n);
+  if ((e = hipMemcpyAsync(fa.data(), d_fa, n * 4ull, hipMemcpyDeviceToHost, ctx->stream)) ||
+      (e = hipMemcpyAsync(fv.data(), d_fv, n * 8ull, hipMemcpyDeviceToHost, ctx->stream)) ||
+      (e = stream_wait(ctx->stream)))
+    return ctx->hip_fail(e, "gate");
+  for (uint32_t i = 0; i < n; i++)
+    if (fa[i] >= m) return ctx->fail(CE_ERR_INVALID_ARG, "file_actor out of range");
+  for (uint32_t a = 0; a < m; a++) expect[a] = c->nov[wslot[a]];
+  const uint32_t first_gap = host_gate(fa.data(), fv.data(), n, &expect, ap.data());
+  if ((e = hipMemcpyAsync(ctx->apply.p, ap.data(), n, hipMemcpyHostToDevice, ctx->stream)) ||
+      (e = stream_wait(ctx->stream)))
+    return ctx->hip_fail(e, "gate");
+  // 2) single-page files: opened, checked and decoded in one kernel, the plaintext in LDS
+  //    (k_open_fold_v3's GS form, lib.rs:501-507), the gated files' members into the batch table;
+  //    larger files: opened to HBM by the segment pass and decoded whole by k_decode_gset
+  uint32_t ec = 0;
+  if ((rc = device_open_setup(ctx, d_blob, d_offs, n, blob_len, true, key_of(c), ctx->status.as<int32_t>(), &ec)))
+    return rc;
+  uint32_t* paths = g->meta.as<uint32_t>() + 12;
+  g->h_fused = GsFused{committed(g), batch(g), paths};
+  if ((e = g->fused.reserve(sizeof(GsFused))) || (e = hipMemsetAsync(paths, 0, 12, ctx->stream)) ||
+      (e = hipMemcpyAsync(g->fused.p, &g->h_fused, sizeof(GsFused), hipMemcpyHostToDevice, ctx->stream)))
+    return ctx->hip_fail(e, "gset fused args");
+  DecodeArgs da{};
+  da.pt = ctx->out.as<uint8_t>();
+  da.blob = d_blob;
+  da.params = ctx->params.as<FileParams>();
+  da.status = ctx->status.as<int32_t>();
+  da.n = n;
+  da.supported = c->d_supported.as<uint8_t>();
+  da.n_supported = (uint32_t)c->supported.size();
+  da.apply = ctx->apply.as<uint8_t>();
+  da.counters = ctx->counters.as<uint32_t>();
+  da.aux = ctx->poly_aux.as<PolyAux>();
+  da.gs = g->fused.as<GsFused>();
+  ctx->open_log.grid_cap = test_grid_cap();
+  {
+    hipEvent_t t0, t1;
+    (void)ctx->tlaunch("open_fold_small", &t0, &t1);
+    if ((e = launch_open_fold_gset(ctx->stream, da, ctx->open_log, t0, t1))) return ctx->hip_fail(e, "fused");
+  }
+  g->batch_dirty = true;
+  const SegScratch sc = segscratch(ctx, ec);
+  int t = ctx->tbegin("segments_open");
+  if ((e = launch_segments(ctx->stream, false, d_blob, ctx->out.as<uint8_t>(), ctx->params.as<FileParams>(), n,
+                           ctx->status.as<int32_t>(), sc, grid_waves_for(n + ec), true)))
+    return ctx->hip_fail(e, "open segments");
+  ctx->tend(t);
+  t = ctx->tbegin("finalize_open");
+  if ((e = launch_finalize_multi(ctx->stream, false, ctx->out.as<uint8_t>(), ctx->params.as<FileParams>(),
+                                 ctx->status.as<int32_t>(), sc, n)))
+    return ctx->hip_fail(e, "open finalize");
+  ctx->tend(t);
+  count_open_launches(c, ctx);
+  uint32_t hm[kMetaWords], hc[16];
+  if ((e = hipMemcpyAsync(hc, ctx->counters.p, 64, hipMemcpyDeviceToHost, ctx->stream))) return ctx->hip_fail(e, "counters");
+  if ((rc = read_meta(c, hm))) return rc;
+  std::vector<int32_t> st;
+  if (hm[4 + kGsOverflow]) {
+    // the batch table filled up inside the fused open: grown, then the batch folded again from
+    // plaintext in HBM (inserts are idempotent; every file is opened and checked again)
+    if ((e = hipMemsetAsync(g->meta.as<uint32_t>() + 4 + kGsOverflow, 0, 4, ctx->stream))) return ctx->hip_fail(e, "gset grow");
+    if ((rc = rehash(c, true, g->bcap * 2)) ||
+        (rc = device_open(ctx, d_blob, d_offs, n, blob_len, true, key_of(c), ctx->out.as<uint8_t>(),
+                          ctx->status.as<int32_t>(), false, true)))
+      return rc;
+    count_open_launches(c, ctx);
+    c->path_counts["gset_refolds"]++;
+    if ((rc = download_status(c, n, &st))) return rc;
+    if (std::find(st.begin(), st.end(), kStatusHostParse) != st.end()) {
+      if ((rc = resolve_host_parse(c, d_blob, d_offs, n, true))) return rc;
+    }
+    if ((rc = decode_pass(c, n, nullptr)) || (rc = download_status(c, n, &st))) return rc;
+  } else {
+    c->path_counts["gset_fused_files"] += hm[14];
+    c->path_counts["gset_uniform_files"] += hm[12];
+    c->path_counts["gset_general_files"] += hm[13];
+    if (hc[9] && (rc = decode_pass(c, n, nullptr, true))) return rc;  // files of more than one page
+    if ((rc = download_status(c, n, &st))) return rc;
+    if (std::find(st.begin(), st.end(), kStatusHostParse) != st.end()) {
+      // envelopes left to the host: opened there, the plaintext patched into HBM, decoded from it
+      std::vector<uint8_t> sel(n);
+      for (uint32_t i = 0; i < n; i++) sel[i] = st[i] == kStatusHostParse;
+      if ((rc = resolve_host_parse(c, d_blob, d_offs, n, true))) return rc;
+      if ((e = hipMemcpyAsync(g->only.p, sel.data(), n, hipMemcpyHostToDevice, ctx->stream)) ||
+          (e = stream_wait(ctx->stream)))
+        return ctx->hip_fail(e, "host parse mask");
+      if ((rc = decode_pass(c, n, g->only.as<uint8_t>())) || (rc = download_status(c, n, &st))) return rc;
+    }
+  }
+  // CE_OPEN_MULTI_KEY: files that failed authentication under the latest key, under each other
+  // key of the set in id order (the whole batch is opened again; only those files are decoded)
+  if ((c->flags & CE_OPEN_MULTI_KEY) && !c->alt_keys.empty()) {
+    bool any_auth = false, only_auth = true;
+    for (int32_t s : st) {
+      any_auth |= s == CE_ERR_AUTH;
+      only_auth &= s == CE_OK || s == CE_ERR_AUTH;
+    }
+    if (any_auth && only_auth) {
+      std::vector<int32_t> sk;
+      std::vector<uint8_t> sel(n);
+      for (const AltKey& ak : c->alt_keys) {
+        if (std::find(st.begin(), st.end(), (int32_t)CE_ERR_AUTH) == st.end()) break;
+        const KeyRef kr{ak.version, ak.key.data(), ak.key.size()};
+        if ((rc = device_open(ctx, d_blob, d_offs, n, blob_len, true, kr, ctx->out.as<uint8_t>(),
+                              ctx->status.as<int32_t>(), false)) ||
+            (rc = download_status(c, n, &sk)))
+          return rc;
+        bool opened = false;
+        for (uint32_t i = 0; i < n; i++) opened |= (sel[i] = st[i] == CE_ERR_AUTH && sk[i] == CE_OK) != 0;
+        if (!opened) continue;
+        if ((e = hipMemcpyAsync(g->only.p, sel.data(), n, hipMemcpyHostToDevice, ctx->stream)) ||
+            (e = stream_wait(ctx->stream)))
+          return ctx->hip_fail(e, "multi-key mask");
+        if ((rc = decode_pass(c, n, g->only.as<uint8_t>())) || (rc = download_status(c, n, &sk))) return rc;
+        for (uint32_t i = 0; i < n; i++)
+          if (sel[i]) st[i] = sk[i];
+      }
+    }
+  }
+  if (status_out) std::memcpy(status_out, st.data(), n * 4ull);
+  for (uint32_t i = 0; i < n; i++)
+    if (st[i] != CE_OK) {  // all-or-nothing: the batch table is dropped, the set untouched
+      if ((rc = clear_batch(c))) return rc;
+      return st[i];
+    }
+  // 4) commit, next_op_versions (lib.rs:537-538) and the gap error (lib.rs:527-531)
+  if ((rc = commit_batch(c))) return rc;
+  if (c->table_gen != gen0) refresh_slots(c, actors, m, &wslot);
+  for (uint32_t w = 0; w < m; w++) c->nov[wslot[w]] = std::max(c->nov[wslot[w]], expect[w]);
+  if (first_gap < n) {
+    if (status_out) status_out[first_gap] = CE_ERR_OP_VERSION;
+    return CE_ERR_OP_VERSION;
+  }
+  return CE_OK;
+}
+
+}  // namespace ce

@@ -148,7 +148,12 @@ struct DecodeArgs {
   uint32_t mask;
   unsigned long long* batch;    // [capacity] max counters
   uint32_t* counters;           // SegScratch counters
-  uint4* miss_list;             // actors not in the table
+  union {
+    uint4* miss_list;           // actors not in the table
+    const struct GsFused* gs;   // the fused open's GSet form (no actors in its ops): the hash tables
+                                // (ce_gset.h), device memory.  Shares the word so that the
+                                // argument block, and with it every other kernel's code, stays as it was
+  };
   uint32_t miss_cap;
   uint8_t* refold;              // per file: had a miss
   const uint8_t* only;          // null, or per-file: process only files with only[i] != 0
@@ -217,6 +222,9 @@ hipError_t launch_open_fold_v2(hipStream_t s, const DecodeArgs& a, int files_per
 // only one this kind takes): needs a.aux
 hipError_t launch_open_fold_pn(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log,
                                hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// the GSet form (Vec<u64> decoded from LDS into the hash tables of a.gs): needs a.aux and a.gs
+hipError_t launch_open_fold_gset(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log,
+                                 hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 // open only: single-page files (<= kSmallMax) into a.pt at their out_off, 16 lanes per file
 // (k_open_fold_v2<..., DEC = false>); statuses and the failure counters as the segment pass sets them
 hipError_t launch_open_small_v2(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log);

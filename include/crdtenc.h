@@ -205,7 +205,7 @@ enum ce_state_kind {
                             ascending, deferred clocks by their msgpack bytes): the reference's
                             HashMap order is random                           */
   CE_STATE_MVREG = 3,    /* MVReg<u64, Uuid>: op = mvreg::Op::Put{clock, val}                 */
-  CE_STATE_PNCOUNTER = 4 /* PNCounter<Uuid> {p, n: GCounter}: op = pncounter::Op {dot, dir: Pos |
+  CE_STATE_PNCOUNTER = 4,/* PNCounter<Uuid> {p, n: GCounter}: op = pncounter::Op {dot, dir: Pos |
                             Neg}.  Every ce_core_* entry point that takes a GCounter core takes
                             this kind with the same contract, except the dense multi-GPU
                             exchange: ce_core_dense_ready returns 0, and ce_core_export_dense,
@@ -214,6 +214,17 @@ enum ce_state_kind {
                             CE_ERR_INVALID_ARG and touch nothing (ce_core_export_columns_device
                             as for any non-Orswot kind).  Ranks exchange
                             ce_core_state_bytes_device / ce_core_merge_state_device instead.     */
+  CE_STATE_GSET = 5      /* GSet<u64> {value: BTreeSet<u64>}: op = a member (an op file is a
+                            Vec<u64>, any non-negative msgpack integer form).  The members live in
+                            a device hash set (CE_GSET_CAP=<slots>: its starting capacity, read
+                            at ce_core_open); a rejected batch leaves the set and
+                            next_op_versions as they were.  Entry points and the multi-GPU
+                            answers as for CE_STATE_PNCOUNTER.  The state is written in BTreeSet
+                            order: collected, sorted, encoded and sealed on the device
+                            (CE_HOST_COMPACT=1: encoded by the host writer, the cross-check).
+                            ce_core_path_count keys: gset_fused_files (decoded inside the fused
+                            open), gset_uniform_files, gset_general_files, gset_refolds,
+                            gset_grows, gset_batch_grows, gset_device_writes.                    */
 };
 
 enum ce_open_flags {
