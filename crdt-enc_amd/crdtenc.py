@@ -62,6 +62,7 @@ EXPORTS = [
     "ce_core_state_bytes_device", "ce_core_merge_state_device", "ce_core_export_columns_device",
     "ce_core_merge_columns_device", "ce_core_ingest_states_device",
     "ce_core_compact_into_async", "ce_core_compact_wait", "ce_host_alloc", "ce_host_free", "ce_content_names",
+    "ce_core_gset_ingest_ops_device_sharded", "ce_core_gset_pending_members", "ce_core_gset_pending_commit",
 ]
 
 
@@ -958,6 +959,37 @@ class Core:
                                                     ctypes.c_void_p(d_import) if d_import else None,
                                                     ctypes.c_uint64(import_words)),
                        "pending_commit")
+
+    # ---- CE_STATE_GSET partitioned by op-file address (shard.ingest_gset_sharded) ----
+    def gset_ingest_ops_device_sharded(self, d_blob, d_offs, n, blob_len, actors, d_fa, d_fv, d_hi,
+                                       want_status=False):
+        st = (ctypes.c_int32 * max(n, 1))() if want_status else None
+        rc = lib().ce_core_gset_ingest_ops_device_sharded(
+            self.p, ctypes.c_void_p(d_blob), ctypes.c_void_p(d_offs), ctypes.c_uint32(n),
+            ctypes.c_uint64(blob_len), _ptr(actors)[0], ctypes.c_uint32(len(actors) // 16),
+            ctypes.c_void_p(d_fa), ctypes.c_void_p(d_fv), ctypes.c_void_p(d_hi), st)
+        return (rc, list(st)[:n]) if want_status else rc
+
+    def gset_pending_members(self, d_dst, cap):
+        """The pending batch's members into d_dst (device u64[cap], unordered, 0 an ordinary value):
+        (rc, n); rc INVALID_ARG with the needed count when cap is too small (d_dst None, cap 0: the
+        size query), and with n = 0 when nothing is pending."""
+        n = ctypes.c_uint64(0)
+        rc = lib().ce_core_gset_pending_members(self.p, ctypes.c_void_p(d_dst) if d_dst else None,
+                                                ctypes.c_uint64(cap), ctypes.byref(n))
+        return rc, n.value
+
+    def gset_pending_commit(self, accept, parts=(), counts=()):
+        """accept: the committed set takes the local pending batch and the remote columns (device
+        pointers or None, member counts; at most 64); else the pending batch is dropped.  Returns
+        the status."""
+        k = len(parts)
+        if len(counts) != k:
+            raise ValueError("one count per part")
+        ptrs = (ctypes.c_void_p * max(k, 1))(*parts)
+        cs = (ctypes.c_uint64 * max(k, 1))(*counts)
+        return lib().ce_core_gset_pending_commit(self.p, 1 if accept else 0, ptrs if k else None,
+                                                 cs if k else None, ctypes.c_uint32(k))
 
     def writer_versions(self, actors):
         import numpy as np

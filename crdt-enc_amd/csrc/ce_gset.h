@@ -55,6 +55,16 @@ struct GsFused {
 hipError_t launch_decode_gset(hipStream_t s, const GsDecodeArgs& a, uint32_t grid_waves);
 // keys[0..n) into t (a state file's members, local ops)
 hipError_t launch_gs_insert(hipStream_t s, GsTable t, const unsigned long long* keys, uint32_t n);
+// k <= kGsMaxParts columns (other ranks' pending members) for one launch: part[i] holds
+// pre[i + 1] - pre[i] keys, pre[0] = 0, pre[k] = their total (<= 2^31)
+static constexpr uint32_t kGsMaxParts = 64;
+struct GsParts {
+  const unsigned long long* part[kGsMaxParts];
+  uint32_t pre[kGsMaxParts + 1];
+  uint32_t k;
+};
+// every key of every part into t, one launch
+hipError_t launch_gs_insert_parts(hipStream_t s, GsTable t, const GsParts& ps);
 // every member of src into dst (the batch's commit, and a growth's rehash)
 hipError_t launch_gs_move(hipStream_t s, GsTable src, GsTable dst);
 // the live members of t, in no order, into out[0..*n_out) (*n_out zero before the launch)

@@ -139,6 +139,48 @@ __global__ __launch_bounds__(256) void k_gs_insert(GsTable t, const unsigned lon
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) gs_insert(t, keys[i]);
 }
 
+// up to kGsMaxParts columns into t in one launch: a grid-stride loop over their concatenation,
+// the part boundaries (a prefix array) and base pointers staged once into LDS, a lane's part found
+// by a binary search over the prefix.  Four elements per lane and round: their keys, then their
+// first probes, are issued together (the fused open's uniform path does the same); a first probe
+// that finds the key settles the element, anything else takes gs_insert's full probe and claim.
+__global__ __launch_bounds__(256) void k_gs_insert_parts(GsTable t, GsParts ps) {
+  __shared__ uint32_t s_pre[kGsMaxParts + 1];
+  __shared__ const unsigned long long* s_ptr[kGsMaxParts];
+  if (threadIdx.x <= ps.k) s_pre[threadIdx.x] = ps.pre[threadIdx.x];
+  if (threadIdx.x < ps.k) s_ptr[threadIdx.x] = ps.part[threadIdx.x];
+  __syncthreads();
+  const uint32_t total = ps.pre[ps.k];
+  const uint32_t stride = gridDim.x * 256;
+  // (base <= total - 1 and 4 * stride <= 2^22, the sum below stays far from 2^32: total <= 2^31)
+  for (uint32_t base = blockIdx.x * 256 + threadIdx.x; base < total; base += 4 * stride) {
+    unsigned long long v[4], s[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t i = base + (uint32_t)j * stride;
+      v[j] = 0;
+      if (i < total) {
+        // the last part with pre[p] <= i (empty parts share a boundary and are skipped by it)
+        uint32_t lo = 0, hi = ps.k;
+        while (hi - lo > 1) {
+          const uint32_t mid = (lo + hi) >> 1;
+          if (s_pre[mid] <= i) lo = mid;
+          else hi = mid;
+        }
+        v[j] = s_ptr[lo][i - s_pre[lo]];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) s[j] = ld_slot(&t.slots[gs_hash(v[j]) & t.mask]);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (base + (uint32_t)j * stride >= total) continue;
+      if (v[j] != 0 && s[j] == v[j]) continue;
+      gs_insert(t, v[j]);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void k_gs_move(GsTable src, GsTable dst) {
   if (blockIdx.x == 0 && threadIdx.x == 0 && src.meta[kGsZero]) gs_insert(dst, 0);
   const uint32_t cap = src.mask + 1;
@@ -208,6 +250,13 @@ hipError_t launch_decode_gset(hipStream_t s, const GsDecodeArgs& a, uint32_t gri
 hipError_t launch_gs_insert(hipStream_t s, GsTable t, const unsigned long long* keys, uint32_t n) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_gs_insert, dim3(blocks_for(n)), dim3(256), 0, s, t, keys, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_gs_insert_parts(hipStream_t s, GsTable t, const GsParts& ps) {
+  if (ps.k == 0 || ps.pre[ps.k] == 0) return hipSuccess;
+  // four elements per lane and round
+  hipLaunchKernelGGL(k_gs_insert_parts, dim3(blocks_for((ps.pre[ps.k] + 3) / 4)), dim3(256), 0, s, t, ps);
   return hipGetLastError();
 }
 

@@ -9,6 +9,12 @@
 // failure clears the batch table and the committed set is untouched; otherwise k_gs_move commits
 // the batch table's members.  Growth: a launch that raised the overflow flag is run again after
 // the host rehashed the table into twice the capacity (inserts are idempotent).
+//
+// Sharded (a batch partitioned across ranks by op-file address, at the end of this file): the same
+// fold with the ranks' agreed windows as the gate (k_gate_window), after which the batch table
+// stays PENDING; the ranks exchange its members as u64 columns (ce_core_gset_pending_members) and
+// each commits its own batch table and the others' columns, or every rank drops its batch
+// (ce_core_gset_pending_commit).
 #include <algorithm>
 #include <cstring>
 
@@ -16,6 +22,7 @@
 #include "ce_dotset.h"
 #include "ce_dotset_io.h"
 #include "ce_gset.h"
+#include "ce_shard.h"
 
 namespace ce {
 
@@ -25,6 +32,7 @@ struct GsState {
   uint32_t cap = 0, bcap = 0;
   bool batch_dirty = false;
   DevBuf col, sorted, vals, sort_tmp, scan_tmp, only;
+  DevBuf gate;      // the sharded gate's block: e0 u64[m] | newnov u64[m]
   DevBuf fused;     // GsFused: what the fused open reads through DecodeArgs.gs
   GsFused h_fused;  // its host copy (lives through the upload)
 };
@@ -216,6 +224,7 @@ int gs_reset(ce_core* c) {
   if ((e = hipMemsetAsync(g->slots.p, 0, (size_t)g->cap * 8, c->ctx->stream)) ||
       (e = hipMemsetAsync(g->meta.p, 0, kMetaWords * 4, c->ctx->stream)))
     return c->ctx->hip_fail(e, "gset reset");
+  c->pending = false;  // a pending sharded batch goes with the set
   return clear_batch(c);
 }
 
@@ -388,30 +397,49 @@ int gs_compact_device(ce_core* c, std::vector<uint8_t> head, const uint8_t* oute
   return CE_OK;
 }
 
-int gs_ingest_ops(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n,
-                  uint64_t blob_len, const uint8_t* actors, uint32_t m, const uint32_t* d_fa,
-                  const uint64_t* d_fv, int32_t* status_out) {
+namespace {
+
+// what the gate leaves for the commit: the writers' slots, next_op_versions after the applied
+// files (lib.rs:537-538) and where the fold stopped
+struct GsGate {
+  std::vector<uint32_t> wslot;
+  uint64_t gen0 = 0;
+  std::vector<uint64_t> expect;
+  uint32_t first_gap = 0xffffffffu;  // host gate: the file at the gap (n: none)
+  bool gap = false;                  // window gate: the windows stop at a gap
+};
+
+// writers get slots first (the gate is keyed by them); the batch's scratch; a batch table left
+// by an earlier ingest (rejected, or pending and never committed) is dropped
+int prepare_ingest(ce_core* c, uint32_t n, uint64_t blob_len, const uint8_t* actors, uint32_t m, GsGate* gt) {
   ce_ctx* ctx = c->ctx;
   GsState* g = c->gs;
   hipError_t e;
   int rc;
-  // writers get slots first (the gate is keyed by them)
-  std::vector<uint32_t> wslot(m);
-  const uint64_t gen0 = c->table_gen;
+  gt->wslot.resize(m);
+  gt->gen0 = c->table_gen;
   for (uint32_t a = 0; a < m; a++) {
     Uuid u;
     std::memcpy(u.data(), actors + 16ull * a, 16);
-    if ((rc = insert_actor(c, u, &wslot[a]))) return rc;
+    if ((rc = insert_actor(c, u, &gt->wslot[a]))) return rc;
   }
-  if (c->table_gen != gen0) refresh_slots(c, actors, m, &wslot);
+  if (c->table_gen != gt->gen0) refresh_slots(c, actors, m, &gt->wslot);
   if ((rc = table_upload(c)) || (rc = ensure_supported(c))) return rc;
   if ((e = ctx->out.reserve(blob_len + 16ull * n + 128)) || (e = ctx->status.reserve(n * 4ull + 64)) ||
       (e = ctx->apply.reserve(n + 64)) || (e = g->only.reserve(n + 64)))
     return ctx->hip_fail(e, "ingest reserve");
   if (g->batch_dirty && (rc = clear_batch(c))) return rc;
-  // 1) the version gate (lib.rs:519-538) on the host: it needs no plaintext
+  gt->expect.resize(m);
+  for (uint32_t a = 0; a < m; a++) gt->expect[a] = c->nov[gt->wslot[a]];
+  return CE_OK;
+}
+
+// the version gate (lib.rs:519-538) on the host: it needs no plaintext
+int gate_host(ce_core* c, uint32_t n, uint32_t m, const uint32_t* d_fa, const uint64_t* d_fv, GsGate* gt) {
+  ce_ctx* ctx = c->ctx;
+  hipError_t e;
   std::vector<uint32_t> fa(n);
-  std::vector<uint64_t> fv(n), expect(m);
+  std::vector<uint64_t> fv(n);
   std::vector<uint8_t> ap(n);
   if ((e = hipMemcpyAsync(fa.data(), d_fa, n * 4ull, hipMemcpyDeviceToHost, ctx->stream)) ||
       (e = hipMemcpyAsync(fv.data(), d_fv, n * 8ull, hipMemcpyDeviceToHost, ctx->stream)) ||
@@ -419,14 +447,63 @@ int gs_ingest_ops(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uin
     return ctx->hip_fail(e, "gate");
   for (uint32_t i = 0; i < n; i++)
     if (fa[i] >= m) return ctx->fail(CE_ERR_INVALID_ARG, "file_actor out of range");
-  for (uint32_t a = 0; a < m; a++) expect[a] = c->nov[wslot[a]];
-  const uint32_t first_gap = host_gate(fa.data(), fv.data(), n, &expect, ap.data());
+  gt->first_gap = host_gate(fa.data(), fv.data(), n, &gt->expect, ap.data());
   if ((e = hipMemcpyAsync(ctx->apply.p, ap.data(), n, hipMemcpyHostToDevice, ctx->stream)) ||
       (e = stream_wait(ctx->stream)))
     return ctx->hip_fail(e, "gate");
-  // 2) single-page files: opened, checked and decoded in one kernel, the plaintext in LDS
-  //    (k_open_fold_v3's GS form, lib.rs:501-507), the gated files' members into the batch table;
-  //    larger files: opened to HBM by the segment pass and decoded whole by k_decode_gset
+  return CE_OK;
+}
+
+// the sharded gate on the device: apply[i] = e0 <= version < d_hi[writer] (k_gate_window over the
+// windows every rank agreed on).  The host reads back the m window ends and the flags word, no
+// per-file metadata.  CE_ERR_SHARD (flags kShardBad / kShardE0Mismatch): nothing may be folded.
+int gate_window(ce_core* c, uint32_t n, uint32_t m, const uint32_t* d_fa, const uint64_t* d_fv,
+                const uint64_t* d_hi, GsGate* gt) {
+  ce_ctx* ctx = c->ctx;
+  GsState* g = c->gs;
+  hipError_t e;
+  // gate block: e0 u64[m] | newnov u64[m]
+  if ((e = g->gate.reserve(16ull * m + 64)) || (e = ctx->counters.reserve(256)))
+    return ctx->hip_fail(e, "gate reserve");
+  uint8_t* gb = g->gate.as<uint8_t>();
+  GateArgs ga{};
+  ga.fa = d_fa;
+  ga.fv = d_fv;
+  ga.n = n;
+  ga.m = m;
+  ga.e0 = reinterpret_cast<const uint64_t*>(gb);
+  ga.newnov = reinterpret_cast<unsigned long long*>(gb + 8ull * m);
+  ga.apply = ctx->apply.as<uint8_t>();
+  std::vector<uint64_t> hi(m + 1);
+  const int t = ctx->tbegin("gate");
+  if ((m && (e = hipMemcpyAsync(gb, gt->expect.data(), 8ull * m, hipMemcpyHostToDevice, ctx->stream))) ||
+      (e = launch_gate_window(ctx->stream, ga, d_hi, ctx->counters.as<uint32_t>())))
+    return ctx->hip_fail(e, "gate");
+  ctx->tend(t);
+  if ((e = hipMemcpyAsync(hi.data(), d_hi, (m + 1) * 8ull, hipMemcpyDeviceToHost, ctx->stream)) ||
+      (e = stream_wait(ctx->stream)))
+    return ctx->hip_fail(e, "gate");
+  if (hi[m] & (kShardBad | kShardE0Mismatch))
+    return ctx->fail(CE_ERR_SHARD, hi[m] & kShardE0Mismatch
+                                       ? "ranks started from different next_op_versions"
+                                       : "a rank's batch breaks the partition contract: exact windows needed");
+  for (uint32_t a = 0; a < m; a++) gt->expect[a] = std::max(gt->expect[a], hi[a]);
+  gt->gap = (hi[m] & kShardGap) != 0;
+  return CE_OK;
+}
+
+// Every file opened, checked and decoded whatever the gate says, the gated files' members (apply[],
+// already on the device) into the batch table.  A failing file: its status is returned, the batch
+// table is cleared and the committed set untouched (all-or-nothing, lib.rs:497-514).
+int fold_batch(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n, uint64_t blob_len,
+               int32_t* status_out) {
+  ce_ctx* ctx = c->ctx;
+  GsState* g = c->gs;
+  hipError_t e;
+  int rc;
+  // single-page files: opened, checked and decoded in one kernel, the plaintext in LDS
+  // (k_open_fold_v3's GS form, lib.rs:501-507), the gated files' members into the batch table;
+  // larger files: opened to HBM by the segment pass and decoded whole by k_decode_gset
   uint32_t ec = 0;
   if ((rc = device_open_setup(ctx, d_blob, d_offs, n, blob_len, true, key_of(c), ctx->status.as<int32_t>(), &ec)))
     return rc;
@@ -538,15 +615,174 @@ int gs_ingest_ops(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uin
       if ((rc = clear_batch(c))) return rc;
       return st[i];
     }
-  // 4) commit, next_op_versions (lib.rs:537-538) and the gap error (lib.rs:527-531)
+  return CE_OK;
+}
+
+}  // namespace
+
+int gs_ingest_ops(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n,
+                  uint64_t blob_len, const uint8_t* actors, uint32_t m, const uint32_t* d_fa,
+                  const uint64_t* d_fv, int32_t* status_out) {
+  GsGate gt;
+  int rc;
+  if ((rc = prepare_ingest(c, n, blob_len, actors, m, &gt)) || (rc = gate_host(c, n, m, d_fa, d_fv, &gt)) ||
+      (rc = fold_batch(c, d_blob, d_offs, n, blob_len, status_out)))
+    return rc;
+  // commit, next_op_versions (lib.rs:537-538) and the gap error (lib.rs:527-531)
   if ((rc = commit_batch(c))) return rc;
-  if (c->table_gen != gen0) refresh_slots(c, actors, m, &wslot);
-  for (uint32_t w = 0; w < m; w++) c->nov[wslot[w]] = std::max(c->nov[wslot[w]], expect[w]);
-  if (first_gap < n) {
-    if (status_out) status_out[first_gap] = CE_ERR_OP_VERSION;
+  if (c->table_gen != gt.gen0) refresh_slots(c, actors, m, &gt.wslot);
+  for (uint32_t w = 0; w < m; w++) c->nov[gt.wslot[w]] = std::max(c->nov[gt.wslot[w]], gt.expect[w]);
+  if (gt.first_gap < n) {
+    if (status_out) status_out[gt.first_gap] = CE_ERR_OP_VERSION;
     return CE_ERR_OP_VERSION;
   }
   return CE_OK;
 }
 
+// The sharded ingest (crdtenc shard.ingest_gset_sharded): the same fold with the agreed windows
+// as the gate, the batch table left PENDING for ce_core_gset_pending_members / _commit.
+static int gs_ingest_ops_sharded(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n,
+                                 uint64_t blob_len, const uint8_t* actors, uint32_t m, const uint32_t* d_fa,
+                                 const uint64_t* d_fv, const uint64_t* d_hi, int32_t* status_out) {
+  GsGate gt;
+  int rc;
+  c->pending = false;
+  if (!c->has_key) return c->ctx->fail(CE_ERR_NO_KEY, "no latest key");
+  if (n) {
+    if ((rc = prepare_ingest(c, n, blob_len, actors, m, &gt))) return rc;
+  } else {
+    // no file on this rank: the windows still set next_op_versions, and the pending batch is
+    // empty (no writer needs a slot before the commit)
+    hipError_t e;
+    if ((c->gs->batch_dirty && (rc = clear_batch(c)))) return rc;
+    if ((e = c->ctx->apply.reserve(64))) return c->ctx->hip_fail(e, "ingest reserve");
+    gt.expect.assign(m, 0);
+    for (uint32_t a = 0; a < m; a++) {
+      Uuid u;
+      std::memcpy(u.data(), actors + 16ull * a, 16);
+      auto it = c->slot_of.find(u);
+      if (it != c->slot_of.end()) gt.expect[a] = c->nov[it->second];
+    }
+  }
+  if ((rc = gate_window(c, n, m, d_fa, d_fv, d_hi, &gt))) return rc;
+  if (n && (rc = fold_batch(c, d_blob, d_offs, n, blob_len, status_out))) return rc;
+  // pending until the commit: the windows' next_op_versions (lib.rs:537-538)
+  c->pending_nov.clear();
+  for (uint32_t a = 0; a < m; a++) {
+    Uuid u;
+    std::memcpy(u.data(), actors + 16ull * a, 16);
+    c->pending_nov.push_back({u, gt.expect[a]});
+  }
+  c->pending = true;
+  c->pending_gen = c->table_gen;
+  return gt.gap ? CE_ERR_OP_VERSION : CE_OK;
+}
+
 }  // namespace ce
+
+using namespace ce;
+
+extern "C" {
+
+int ce_core_gset_ingest_ops_device_sharded(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n,
+                                           uint64_t blob_len, const uint8_t* actors, uint32_t m,
+                                           const uint32_t* d_fa, const uint64_t* d_fv, const uint64_t* d_hi,
+                                           int32_t* status) {
+  if (!c || (n && (!d_blob || !d_offs || !d_fa || !d_fv)) || (m && !actors) || !d_hi || c->kind != CE_STATE_GSET)
+    return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  return gs_ingest_ops_sharded(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, d_hi, status);
+}
+
+int ce_core_gset_pending_members(ce_core* c, uint64_t* d_dst, uint64_t cap_members, uint64_t* n) {
+  if (!c || !n || c->kind != CE_STATE_GSET) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  *n = 0;
+  if (!c->pending) return c->ctx->fail(CE_ERR_INVALID_ARG, "no pending batch");
+  GsState* g = c->gs;
+  hipStream_t s = c->ctx->stream;
+  uint32_t hm[kMetaWords];
+  int rc = read_meta(c, hm);
+  if (rc) return rc;
+  *n = (uint64_t)hm[4 + kGsCount] + (hm[4 + kGsZero] ? 1u : 0u);
+  if (*n == 0) return CE_OK;
+  if (!d_dst || cap_members < *n) return CE_ERR_INVALID_ARG;  // (the size query: *n = what it takes)
+  uint32_t* n_out = g->meta.as<uint32_t>() + 15;
+  hipError_t e;
+  const int t = c->ctx->tbegin("gset_export");
+  if ((e = hipMemsetAsync(n_out, 0, 4, s)) ||
+      (e = launch_gs_collect(s, batch(g), reinterpret_cast<unsigned long long*>(d_dst), n_out)))
+    return c->ctx->hip_fail(e, "gset export");
+  c->ctx->tend(t);
+  // the caller's collective may run on another stream: the column is complete on return
+  if ((e = stream_wait(s))) return c->ctx->hip_fail(e, "gset export");
+  return CE_OK;
+}
+
+int ce_core_gset_pending_commit(ce_core* c, int accept, const uint64_t* const* d_parts, const uint64_t* counts,
+                                uint32_t k) {
+  if (!c || c->kind != CE_STATE_GSET) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  ce_ctx* ctx = c->ctx;
+  if (!c->pending) return ctx->fail(CE_ERR_INVALID_ARG, "no pending batch");
+  // the arguments first: a refused call leaves the batch pending
+  if (k > kGsMaxParts || (k && (!d_parts || !counts))) return ctx->fail(CE_ERR_INVALID_ARG, "at most 64 parts");
+  uint64_t remote = 0;
+  for (uint32_t i = 0; i < k; i++) {
+    if (counts[i] && !d_parts[i]) return ctx->fail(CE_ERR_INVALID_ARG, "a null part with members");
+    if (counts[i] > (1ull << 30) || (remote += counts[i]) > (1ull << 30))
+      return ctx->fail(CE_ERR_INVALID_ARG, "set too large for the table");
+  }
+  GsState* g = c->gs;
+  hipStream_t s = ctx->stream;
+  c->pending = false;
+  if (!accept) return clear_batch(c);  // another rank's batch failed: the state stays unchanged
+  uint32_t hm[kMetaWords];
+  int rc = read_meta(c, hm);
+  if (rc) return rc;
+  // grown once, before any insert, to the upper bound (duplicates are unknown): neither the move
+  // nor the inserts can meet the load bound
+  if ((rc = ensure_committed(c, hm[kGsCount], (uint64_t)hm[4 + kGsCount] + remote))) return rc;
+  hipError_t e;
+  int t = ctx->tbegin("gset_commit");
+  if ((hm[4 + kGsCount] || hm[4 + kGsZero]) && (e = launch_gs_move(s, batch(g), committed(g))))
+    return ctx->hip_fail(e, "gset commit");
+  ctx->tend(t);
+  if (remote) {
+    // CE_GSET_PART_LAUNCHES=1: one k_gs_insert launch per part, the form the single launch was
+    // measured against (tools/gset_shard_bench.py)
+    const char* pl = getenv("CE_GSET_PART_LAUNCHES");
+    t = ctx->tbegin("gset_parts");
+    if (pl && atoi(pl)) {
+      for (uint32_t i = 0; i < k; i++)
+        if ((e = launch_gs_insert(s, committed(g), reinterpret_cast<const unsigned long long*>(d_parts[i]),
+                                  (uint32_t)counts[i])))
+          return ctx->hip_fail(e, "gset commit");
+    } else {
+      GsParts ps{};
+      ps.k = k;
+      for (uint32_t i = 0; i < k; i++) {
+        ps.part[i] = reinterpret_cast<const unsigned long long*>(d_parts[i]);
+        ps.pre[i + 1] = ps.pre[i] + (uint32_t)counts[i];
+      }
+      if ((e = launch_gs_insert_parts(s, committed(g), ps))) return ctx->hip_fail(e, "gset commit");
+    }
+    ctx->tend(t);
+  }
+  if ((rc = clear_batch(c))) return rc;
+  for (auto& p : c->pending_nov) {  // next_op_versions.inc per applied file (lib.rs:537-538)
+    if (p.second == 0) continue;   // nothing applied and nothing known: no entry (VClock::get = 0)
+    uint32_t slot;
+    if ((rc = insert_actor(c, p.first, &slot))) return rc;
+    c->nov[slot] = std::max(c->nov[slot], p.second);
+  }
+  if ((rc = table_upload(c))) return rc;
+  // the parts are the caller's buffers: read by the time this returns
+  if ((e = stream_wait(s))) return ctx->hip_fail(e, "gset commit");
+  return CE_OK;
+}
+
+}  // extern "C"

@@ -14,6 +14,10 @@ every rank's state unchanged (lib.rs:497-514), otherwise each rank commits the r
 A Dot naming an actor outside the registered slots sends every rank to the all-gather of
 serialized states instead.
 
+GSet<u64>: the same partition and the same gate (ingest_gset_sharded); the pending batch is the
+set of members the committed set lacks, so after one small all-gather of every rank's outcome the
+ranks all-gather those members as plain u64 columns and each commits the others' (or none does).
+
 Writer sharding (actor_range / file_rank) is kept for the dot-set kinds (below) and as the
 previous layout of the VClock path (exchange_vclock after a local ingest).
 
@@ -415,9 +419,10 @@ ERR_OP_VERSION, ERR_SHARD = 13, 69
 SHARD_BAD, SHARD_GAP, SHARD_E0_MISMATCH = 1, 2, 4
 
 
-class DeviceShardOps:
-    """The sharded-ingest steps of a crdtenc.Core over this rank's batch resident in HBM
-    (torch tensors: files u8, offs i64[n+1], fa i32[n] into the shared writer list, fv i64[n])."""
+class _DeviceShardBase:
+    """The window steps of a crdtenc.Core over this rank's batch resident in HBM (torch tensors:
+    files u8, offs i64[n+1], fa i32[n] into the shared writer list, fv i64[n]): the same for every
+    kind the gate takes."""
 
     def __init__(self, core, actors, files, offs, n, blob_len, fa, fv):
         self.core, self.actors = core, actors
@@ -428,7 +433,6 @@ class DeviceShardOps:
         self.device = fa.device
         self.stats = torch.empty(2 * self.m + 3, dtype=torch.int64, device=self.device)
         self.hi = torch.empty(self.m + 1, dtype=torch.int64, device=self.device)
-        self.dense = torch.empty(core.dense_capacity() + 2, dtype=torch.int64, device=self.device)
 
     def _ordered(self):
         """The core runs on its context's stream: when that is not torch's current stream, what
@@ -458,6 +462,15 @@ class DeviceShardOps:
 
     def writer_versions(self):
         return self.core.writer_versions(self.actors)
+
+
+class DeviceShardOps(_DeviceShardBase):
+    """The sharded-ingest steps of a VClock / GCounter crdtenc.Core: the pending batch is a dense
+    array over the registered slots."""
+
+    def __init__(self, core, actors, files, offs, n, blob_len, fa, fv):
+        super().__init__(core, actors, files, offs, n, blob_len, fa, fv)
+        self.dense = torch.empty(core.dense_capacity() + 2, dtype=torch.int64, device=self.device)
 
     def ingest(self):
         r = self.core.ingest_ops_device_sharded(self.files.data_ptr(), self.offs.data_ptr(), self.n,
@@ -512,14 +525,10 @@ def _gather_metadata(fa, fv, group=None):
     return np.concatenate(fas), np.concatenate(fvs)
 
 
-def ingest_sharded(ops, group=None, exchange_bytes=None):
-    """read_remote_ops (crdt-enc/src/lib.rs:471-547) over a batch partitioned across the ranks by
-    op-file address.  `ops`: a DeviceShardOps (or the CPU test's twin).  Every rank ends with the
-    state the reference reaches folding the whole batch in (shared writer order, version) order.
-    Returns (rc, path): rc 0, CE_ERR_OP_VERSION (the fold stopped at a gap; the files before it
-    are folded on every rank) or the failing status (every rank's state unchanged); path
-    "dense" | "bytes" (state all-gather) | "rejected", plus "+exact" when the windows came from
-    the gathered metadata."""
+def _agree_windows(ops, group=None):
+    """The gate of a sharded ingest: per-writer stats, one all_reduce(MAX), identical windows on
+    every rank, left in `ops` (window / set_window).  Returns "" (the windows from the reduced
+    stats), "+exact" (from everyone's gathered metadata) or None (refused: nothing to fold)."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     # 1) the gate: per-writer stats, one all_reduce(MAX), identical windows on every rank
     stats = ops.compute_stats(rank, world)
@@ -531,7 +540,7 @@ def ingest_sharded(ops, group=None, exchange_bytes=None):
     if flags & SHARD_E0_MISMATCH:
         # the ranks started from different next_op_versions: no window is right for all of them
         # (the exact fallback would compute each rank's from its own e0); refused, nothing folded
-        return ERR_SHARD, "refused"
+        return None
     exact = ""
     if flags & SHARD_BAD:
         # a rank's batch breaks the partition contract: the windows from everyone's metadata,
@@ -545,6 +554,20 @@ def ingest_sharded(ops, group=None, exchange_bytes=None):
         exact = "+exact"
     else:
         ops.window()
+    return exact
+
+
+def ingest_sharded(ops, group=None, exchange_bytes=None):
+    """read_remote_ops (crdt-enc/src/lib.rs:471-547) over a batch partitioned across the ranks by
+    op-file address.  `ops`: a DeviceShardOps (or the CPU test's twin).  Every rank ends with the
+    state the reference reaches folding the whole batch in (shared writer order, version) order.
+    Returns (rc, path): rc 0, CE_ERR_OP_VERSION (the fold stopped at a gap; the files before it
+    are folded on every rank) or the failing status (every rank's state unchanged); path
+    "dense" | "bytes" (state all-gather) | "rejected", plus "+exact" when the windows came from
+    the gathered metadata."""
+    exact = _agree_windows(ops, group)
+    if exact is None:
+        return ERR_SHARD, "refused"
     # any failure here, including a rank-local early return, reaches every rank through the
     # reduce below, and every rank keeps its state
     rc = ops.ingest()
@@ -569,3 +592,107 @@ def ingest_sharded(ops, group=None, exchange_bytes=None):
     ops.commit(True, dense[:cap])
     return rc, "dense" + exact
 
+
+
+# ---------------------------------------------------------------------------------------------
+# GSet<u64> partitioned by op-file address: the same gate, the pending members exchanged as
+# plain u64 columns
+# ---------------------------------------------------------------------------------------------
+class DeviceGsetShardOps(_DeviceShardBase):
+    """The sharded-ingest steps of a CE_STATE_GSET crdtenc.Core: the pending batch is a hash table
+    of the members the committed set lacks, exported as an unordered u64 column."""
+
+    def ingest(self):
+        r = self.core.gset_ingest_ops_device_sharded(self.files.data_ptr(), self.offs.data_ptr(), self.n,
+                                                     self.blob_len, self.actors, self.fa.data_ptr(),
+                                                     self.fv.data_ptr(), self.hi.data_ptr(),
+                                                     want_status=self.want_status)
+        if self.want_status:
+            r, self.status = r
+        return r
+
+    def pending_count(self):
+        rc, n = self.core.gset_pending_members(None, 0)
+        if rc and not (rc == _ERR_INVALID_ARG and n):
+            raise RuntimeError("gset_pending_members failed: %d" % rc)
+        return n
+
+    def member_buffer(self, n):
+        return torch.empty(n, dtype=torch.int64, device=self.device)
+
+    def export_members(self, t):
+        """The pending members into t (an int64 view of u64, on the core's device); returns their
+        count."""
+        if t.dtype != torch.int64:
+            raise TypeError("members are an int64 view of u64")
+        self._ordered()
+        rc, n = self.core.gset_pending_members(t.data_ptr(), t.numel())
+        if rc:
+            raise RuntimeError("gset_pending_members failed: %d" % rc)
+        return n
+
+    def commit(self, accept, parts=(), counts=()):
+        self._ordered()
+        rc = self.core.gset_pending_commit(accept, [p.data_ptr() if c else None for p, c in zip(parts, counts)],
+                                           list(counts))
+        if rc:
+            raise RuntimeError("gset_pending_commit failed: %d" % rc)
+
+
+def _all_gather_flat(t, group=None):
+    """Every rank's `t` (same length everywhere), concatenated in rank order, on t's device: one
+    all_gather_into_tensor of device tensors under RCCL; gloo gathers host tensors (device ones
+    staged through the host)."""
+    world = dist.get_world_size(group)
+    if t.is_cuda and not _host_staged(t, group):
+        out = torch.empty(world * t.numel(), dtype=t.dtype, device=t.device)
+        dist.all_gather_into_tensor(out, t, group=group)
+        return out
+    h = t.cpu()
+    parts = [torch.empty_like(h) for _ in range(world)]
+    dist.all_gather(parts, h, group=group)
+    return torch.cat(parts).to(t.device)
+
+
+def ingest_gset_sharded(ops, group=None):
+    """read_remote_ops (crdt-enc/src/lib.rs:471-547) of a GSet<u64> over a batch partitioned across
+    the ranks by op-file address.  `ops`: a DeviceGsetShardOps (or the CPU test's twin).  Every
+    rank ends with the state the reference reaches folding the whole batch in (shared writer
+    order, version) order.  Two collectives after the gate's: a small all-gather of every rank's
+    [failure code, pending members], then one all-gather of the member columns (skipped on every
+    rank when nobody has a new member).  Returns (rc, path): rc 0, CE_ERR_OP_VERSION (the fold
+    stopped at a gap; the files before it are folded on every rank) or the failing status (every
+    rank's state unchanged); path "members" | "rejected" | "refused", plus "+exact" when the
+    windows came from the gathered metadata."""
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    if world - 1 > _MAX_COLUMN_PARTS:
+        raise ValueError("ce_core_gset_pending_commit takes at most %d remote columns" % _MAX_COLUMN_PARTS)
+    # 1) the gate: ingest_sharded's
+    exact = _agree_windows(ops, group)
+    if exact is None:
+        return ERR_SHARD, "refused"
+    # 2) this rank's share, left pending
+    rc = ops.ingest()
+    failed = rc not in (0, ERR_OP_VERSION)
+    # 3) the outcome: a rank that failed locally still takes every collective
+    dev = getattr(ops, "device", torch.device("cpu"))
+    if dist.get_backend(group) == "gloo":
+        dev = torch.device("cpu")
+    mine = torch.tensor([rc if failed else 0, 0 if failed else ops.pending_count()], dtype=torch.int64, device=dev)
+    got = _all_gather_flat(mine, group=group).cpu().tolist()
+    codes, counts = got[0::2], got[1::2]
+    if any(codes):
+        if not failed:
+            ops.commit(False)
+        return max(codes), "rejected" + exact
+    # 4) the members: every rank's column, padded to the longest, in one all-gather
+    width = max(counts)
+    if width == 0:
+        ops.commit(True)
+        return rc, "members" + exact
+    buf = ops.member_buffer(width)
+    ops.export_members(buf)
+    every = _all_gather_flat(buf, group=group)
+    others = [r for r in range(world) if r != rank]
+    ops.commit(True, [every[r * width: r * width + counts[r]] for r in others], [counts[r] for r in others])
+    return rc, "members" + exact

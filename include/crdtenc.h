@@ -219,7 +219,9 @@ enum ce_state_kind {
                             a device hash set (CE_GSET_CAP=<slots>: its starting capacity, read
                             at ce_core_open); a rejected batch leaves the set and
                             next_op_versions as they were.  Entry points and the multi-GPU
-                            answers as for CE_STATE_PNCOUNTER.  The state is written in BTreeSet
+                            answers as for CE_STATE_PNCOUNTER, plus its own sharded ingest
+                            (ce_core_gset_ingest_ops_device_sharded and the two ce_core_gset_
+                            pending_* calls below).  The state is written in BTreeSet
                             order: collected, sorted, encoded and sealed on the device
                             (CE_HOST_COMPACT=1: encoded by the host writer, the cross-check).
                             ce_core_path_count keys: gset_fused_files (decoded inside the fused
@@ -468,6 +470,41 @@ int ce_core_pending_export(ce_core *c, uint64_t *d_batch, uint64_t cap_words, in
  * ce_core_dense_capacity) : the local pending batch), next_op_versions from the windows;
  * !accept: drop the pending batch. */
 int ce_core_pending_commit(ce_core *c, int accept, const uint64_t *d_import, uint64_t import_words);
+/* ---- CE_STATE_GSET partitioned by op-file address.  ce_core_shard_stats, ce_core_shard_window
+ * and ce_core_writer_versions take a GSet core as they are; the three calls above keep refusing
+ * it (its batch is a hash table of members, not a dense array), and these take their place. ----
+ *
+ * read_remote_ops (lib.rs:471-547) over this rank's share of a GSet batch, the agreed windows as
+ * the gate (e0 <= version < d_hi[writer], decided on the device; the host reads back the m window
+ * ends and the flags word only); members absent from the committed set are claimed in the batch
+ * table and stay PENDING.  Every file is opened and checked whatever the gate says.  Same return
+ * contract as ce_core_ingest_ops_device_sharded: CE_OK; CE_ERR_OP_VERSION (the windows stop at a
+ * gap, the files before it pending); CE_ERR_SHARD (flags 1 or 4: nothing opened or folded); or the
+ * lowest failing file's status -- then the batch table is cleared and NO pending batch exists
+ * (a later ce_core_gset_pending_members / _commit returns CE_ERR_INVALID_ARG).  n = 0 (a rank
+ * that owns no file): the windows still set next_op_versions and an empty pending batch exists.
+ * While a batch is pending, ce_core_state_bytes*, ce_core_compact* and the content name see the
+ * committed set only; ce_core_apply_ops and ce_core_merge_state insert into the committed set and
+ * leave the batch alone; any ops ingest (sharded or not) and ce_core_reset drop it. */
+int ce_core_gset_ingest_ops_device_sharded(ce_core *c, const uint8_t *d_blob, const uint64_t *d_offs,
+                                           uint32_t n, uint64_t blob_len, const uint8_t *actors,
+                                           uint32_t m, const uint32_t *d_fa, const uint64_t *d_fv,
+                                           const uint64_t *d_hi, int32_t *status);
+/* The pending batch's members as a u64 column in device memory (host byte order), in no
+ * particular order, the member 0 included as an ordinary value.  *n = members written, or needed
+ * when cap_members is too small (CE_ERR_INVALID_ARG, nothing written); d_dst NULL with cap 0 is
+ * the size query (CE_OK with *n = 0 for an empty batch).  No pending batch: CE_ERR_INVALID_ARG,
+ * *n = 0.  Complete on return. */
+int ce_core_gset_pending_members(ce_core *c, uint64_t *d_dst, uint64_t cap_members, uint64_t *n);
+/* accept: committed set |= local pending batch, plus k <= 64 remote columns (d_parts[i], counts[i]
+ * members; k = 0 with NULLs allowed); next_op_versions from the windows (lib.rs:537-538).  The
+ * committed table is grown once, before any insert, to hold its count + the local batch + the sum
+ * of counts (duplicates are unknown), so no insert meets the load bound.  !accept: the pending
+ * batch is dropped and nothing else changes.  k > 64, or a NULL part with a non-zero count:
+ * CE_ERR_INVALID_ARG, checked before anything is touched -- the batch stays pending.  The parts
+ * have been read on return. */
+int ce_core_gset_pending_commit(ce_core *c, int accept, const uint64_t *const *d_parts,
+                                const uint64_t *counts, uint32_t k);
 /* next_op_versions.get(writer) for each of m writers (host) */
 int ce_core_writer_versions(ce_core *c, const uint8_t *actors, uint32_t m, uint64_t *e0_out);
 /* Host twins (CPU ranks, tests): ShardStats over host metadata; the windows from reduced stats;
