@@ -1318,8 +1318,9 @@ int ingest_states_dev(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs,
       break;
     }
   std::vector<FileParams> P(n);
-  if (c->kind == CE_STATE_ORSWOT && !getenv("CE_HOST_STATES")) {
-    // plaintexts stay in HBM: the device reader decodes canonical states (ce_dotset_io.hip)
+  if ((c->kind == CE_STATE_ORSWOT || c->kind == CE_STATE_GSET) && !getenv("CE_HOST_STATES")) {
+    // plaintexts stay in HBM: the device reader decodes canonical states (ce_dotset_io.hip,
+    // ce_gset.hip)
     std::vector<uint64_t> off(n, 0), len(n, 0);
     for (uint32_t i = 0; i < n; i++) {
       if (st[i] != CE_OK) continue;
@@ -1335,6 +1336,8 @@ int ingest_states_dev(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs,
       std::memcpy(v.data(), h + 16, 16);
       if (!std::binary_search(c->supported.begin(), c->supported.end(), v)) st[i] = CE_ERR_PT_VERSION;
     }
+    if (c->kind == CE_STATE_GSET)
+      return gs_merge_states_device(c, ctx->out.as<uint8_t>(), off, len, st.data(), status_out);
     return ds_merge_states_device(c, ctx->out.as<uint8_t>(), off, len, st.data(), status_out);
   }
   std::vector<uint8_t> out(blen + 16ull * n + 64);
@@ -2326,12 +2329,23 @@ int ce_core_merge_state(ce_core* c, const uint8_t* sw, size_t len) {
 }
 
 // ce_core_state_bytes into device memory: Orswot through the device writer (the 35 MB C3
-// partial never crosses PCIe); the other kinds' states are small and serialized on the host.
+// partial never crosses PCIe) and GSet through its own (the members are written in HBM and copied
+// device to device); the other kinds' states are small and serialized on the host.
 int ce_core_state_bytes_device(ce_core* c, uint8_t* d_dst, uint64_t cap, uint64_t* len) {
   if (!c || !len || (cap && !d_dst)) return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
   (void)hipSetDevice(c->ctx->device);
   if (c->kind == CE_STATE_ORSWOT && !c->host_compact) return ds_state_bytes_device(c, c->ctx, d_dst, cap, len);
+  if (c->kind == CE_STATE_GSET && !c->host_compact) {
+    HostPhase hp("gset bytes (all)");
+    std::vector<uint8_t> head;
+    int rc;
+    {
+      HostPhase hh("gset bytes: head");
+      rc = serialize_state(c, &head, true);
+    }
+    return rc ? rc : gs_state_bytes_device(c, std::move(head), d_dst, cap, len);
+  }
   std::vector<uint8_t>& b = c->ser_buf;
   int rc = serialize_state(c, &b);
   if (rc) return rc;
@@ -2346,7 +2360,8 @@ int ce_core_state_bytes_device(ce_core* c, uint8_t* d_dst, uint64_t cap, uint64_
 
 // ce_core_merge_state over a StateWrapper resident in HBM: Orswot through the device state
 // reader (ds_merge_states_device: only the head -- next_op_versions and the clock -- and the
-// deferred tail come to the host); the other kinds download it (small) and merge on the host.
+// deferred tail come to the host), GSet through its own (gs_merge_states_device: the head's prefix
+// comes to the host); the other kinds download it (small) and merge on the host.
 int ce_core_merge_state_device(ce_core* c, const uint8_t* d_sw, uint64_t len) {
   if (!c || (len && !d_sw)) return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
@@ -2354,6 +2369,11 @@ int ce_core_merge_state_device(ce_core* c, const uint8_t* d_sw, uint64_t len) {
   if (c->kind == CE_STATE_ORSWOT && !getenv("CE_HOST_STATES")) {
     int32_t st = CE_OK;
     return ds_merge_states_device(c, d_sw, std::vector<uint64_t>{0}, std::vector<uint64_t>{len}, &st, nullptr);
+  }
+  if (c->kind == CE_STATE_GSET && !getenv("CE_HOST_STATES")) {
+    // the head's prefix comes to the host; the members are read and inserted from d_sw
+    int32_t st = CE_OK;
+    return gs_merge_states_device(c, d_sw, std::vector<uint64_t>{0}, std::vector<uint64_t>{len}, &st, nullptr);
   }
   std::vector<uint8_t> h(len);
   hipError_t e;

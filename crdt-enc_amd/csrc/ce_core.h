@@ -288,6 +288,14 @@ int gs_members_sorted(ce_core* c, std::vector<uint64_t>* out);
 int gs_serialize_device(ce_core* c, std::vector<uint8_t> head, std::vector<uint8_t>* out);
 int gs_compact_device(ce_core* c, std::vector<uint8_t> head, const uint8_t* outer, const uint8_t* nonce,
                       const KeyRef& key, std::vector<uint8_t>* file);
+// gs_serialize_device's bytes left in HBM and copied device to device into d_dst (cap bytes);
+// *len = their length, also when cap is too small (CE_ERR_INVALID_ARG, d_dst untouched)
+int gs_state_bytes_device(ce_core* c, std::vector<uint8_t> head, uint8_t* d_dst, uint64_t cap, uint64_t* len);
+// read_remote_states over StateWrapper plaintexts in HBM (file i at base + off[i], len[i] bytes,
+// st[i] its status so far): heads on the host, canonical bodies decoded and inserted on the
+// device, every other file through the host parser; all or nothing
+int gs_merge_states_device(ce_core* c, const uint8_t* base, const std::vector<uint64_t>& off,
+                           const std::vector<uint64_t>& len, int32_t* st, int32_t* status_out);
 // Vec<u64> as rmp-serde reads it (any non-negative integer form); false: CE_ERR_DECODE
 bool parse_gset_ops(const uint8_t* p, size_t n, std::vector<uint64_t>* out);
 // GSet { value: BTreeSet<u64> }: the reader (any order, duplicates) and the canonical writer

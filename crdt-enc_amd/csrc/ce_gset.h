@@ -65,6 +65,26 @@ struct GsParts {
 };
 // every key of every part into t, one launch
 hipError_t launch_gs_insert_parts(hipStream_t s, GsTable t, const GsParts& ps);
+// The state-file reader (a StateWrapper's `value` array in HBM).  One descriptor per file, offsets
+// from the launch's base pointer; count < 2^29 and blen < 2^32 (the host sends other files to its
+// own parser).  runs: kGsStateRunWords words per file, [0, 5) the lengths of the fixint, cc, cd, ce
+// and cf runs, every word 0xffffffff before the first phase.
+struct GsStateFile {
+  unsigned long long body;  // the first element's byte
+  uint32_t blen;            // bytes from there to the end of the file's plaintext
+  uint32_t count;           // the array header's count
+  uint32_t pre;             // (insert) members of the launch's files before this one
+  uint32_t pad;
+};
+static constexpr uint32_t kGsStateRunWords = 8;
+static constexpr uint32_t kGsStateMaxFiles = 128;  // files of one insert launch
+// the five phases of k_gs_state_runs over n files, back to back (max_count: the largest count)
+hipError_t launch_gs_state_runs(hipStream_t s, const uint8_t* base, const GsStateFile* files, uint32_t n,
+                                uint32_t max_count, uint32_t* runs);
+// the members of k <= kGsStateMaxFiles files whose runs sum to their count (count 0: skipped) into
+// t, total = their members (<= 2^31); runs: the first of these files' words
+hipError_t launch_gs_state_insert(hipStream_t s, GsTable t, const uint8_t* base, const GsStateFile* files, uint32_t k,
+                                  uint32_t total, const uint32_t* runs);
 // every member of src into dst (the batch's commit, and a growth's rehash)
 hipError_t launch_gs_move(hipStream_t s, GsTable src, GsTable dst);
 // the live members of t, in no order, into out[0..*n_out) (*n_out zero before the launch)

@@ -181,6 +181,119 @@ __global__ __launch_bounds__(256) void k_gs_insert_parts(GsTable t, GsParts ps) 
   }
 }
 
+// ---- the state-file reader: a StateWrapper's `value` array decoded from plaintext in HBM --------
+// The body is taken when its elements are unsigned markers whose widths never decrease: runs of
+// positive fixints (1 byte), cc (2), cd (3), ce (5) and cf (9), any of them empty.  Phase p proves
+// run p: with the run starting at (element s, byte o) -- both read from the earlier phases' lengths
+// -- it ends at the first t for which the byte at o + w t is not the run's marker class, the
+// element would pass the end of the file, or s + t is the array's count.  Every t before it has
+// then been checked marker by marker, so the first mismatch is all that counts: an atomicMin.
+__device__ __forceinline__ uint32_t gs_run_width(uint32_t r) { return r == 0 ? 1u : r == 1 ? 2u : r == 2 ? 3u : r == 3 ? 5u : 9u; }
+
+__global__ __launch_bounds__(256) void k_gs_state_runs(const uint8_t* base, const GsStateFile* files, uint32_t n,
+                                                       uint32_t* runs, uint32_t phase) {
+  const uint32_t w = gs_run_width(phase);
+  const uint32_t stride = gridDim.x * 256;
+  for (uint32_t f = blockIdx.y; f < n; f += gridDim.y) {
+    const GsStateFile F = files[f];
+    uint32_t* R = runs + kGsStateRunWords * f;
+    uint32_t s = 0;
+    unsigned long long o = 0;
+    for (uint32_t k = 0; k < phase; k++) {  // (the earlier launches' results)
+      const uint32_t L = R[k];
+      s += L;
+      o += (unsigned long long)L * gs_run_width(k);
+    }
+    const uint32_t rem = F.count - s;  // (a run never passes the count: s <= count)
+    const uint8_t* body = base + F.body;
+    // t = rem is the mismatch that always exists; count < 2^29, so t + stride cannot wrap
+    for (uint32_t t = blockIdx.x * 256 + threadIdx.x; t <= rem; t += stride) {
+      if (t >= ld_word(&R[phase])) break;  // an earlier mismatch is known: nothing from here on counts
+      bool bad = t == rem;
+      if (!bad) {
+        const unsigned long long pos = o + (unsigned long long)w * t;
+        if (pos + w > F.blen) bad = true;  // (checked before the load: no byte past the file is read)
+        else {
+          const uint32_t m = body[pos];
+          bad = phase == 0 ? m > 0x7f : m != 0xcbu + phase;
+        }
+      }
+      if (bad) {
+        // (looked at again after the marker's load: in a phase whose run is empty nearly every
+        // candidate mismatches, and all but the first few find a smaller t already there)
+        if (t < ld_word(&R[phase])) atomicMin(&R[phase], t);
+        break;  // (this thread's later t are larger)
+      }
+    }
+  }
+}
+
+// the members of up to kGsStateMaxFiles proven files into t in one launch, as k_gs_insert_parts
+// takes its columns: a grid-stride loop over the files' concatenation, the element prefix and each
+// file's run table (first element and first byte of every run) staged in LDS, a lane's file by a
+// binary search, its run by the five starts, the element's offset in closed form.  Four elements
+// per lane and round, their payloads, then their first probes, issued together.
+__global__ __launch_bounds__(256) void k_gs_state_insert(GsTable t, const uint8_t* base, const GsStateFile* files,
+                                                         uint32_t k, const uint32_t* runs) {
+  __shared__ uint32_t s_pre[kGsStateMaxFiles + 1];
+  __shared__ unsigned long long s_body[kGsStateMaxFiles];
+  __shared__ uint32_t s_rs[kGsStateMaxFiles][5], s_ro[kGsStateMaxFiles][5];
+  if (threadIdx.x < k) {
+    const GsStateFile F = files[threadIdx.x];
+    s_pre[threadIdx.x] = F.pre;
+    if (threadIdx.x == k - 1) s_pre[k] = F.pre + F.count;
+    s_body[threadIdx.x] = F.body;
+    uint32_t s = 0, o = 0;  // (a proven file's run ends lie inside it: o <= blen < 2^32)
+    for (uint32_t r = 0; r < 5; r++) {
+      s_rs[threadIdx.x][r] = s;
+      s_ro[threadIdx.x][r] = o;
+      const uint32_t L = runs[kGsStateRunWords * threadIdx.x + r];
+      s += L;
+      o += L * gs_run_width(r);
+    }
+  }
+  __syncthreads();
+  const uint32_t total = s_pre[k];
+  const uint32_t stride = gridDim.x * 256;
+  for (uint32_t i0 = blockIdx.x * 256 + threadIdx.x; i0 < total; i0 += 4 * stride) {
+    unsigned long long v[4], s[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t i = i0 + (uint32_t)j * stride;
+      v[j] = 0;
+      if (i < total) {
+        // the last file with pre <= i (files without members share a boundary and are skipped by it)
+        uint32_t lo = 0, hi = k;
+        while (hi - lo > 1) {
+          const uint32_t mid = (lo + hi) >> 1;
+          if (s_pre[mid] <= i) lo = mid;
+          else hi = mid;
+        }
+        const uint32_t e = i - s_pre[lo];
+        uint32_t r = 0;  // the last run that starts at or before e (empty runs share a start)
+#pragma unroll
+        for (uint32_t q = 1; q < 5; q++)
+          if (s_rs[lo][q] <= e) r = q;
+        const uint32_t w = gs_run_width(r);
+        const uint8_t* p = base + s_body[lo] + s_ro[lo][r] + (unsigned long long)(e - s_rs[lo][r]) * w;
+        unsigned long long x = 0;
+        if (w == 1) x = p[0];
+        else
+          for (uint32_t b = 1; b < w; b++) x = (x << 8) | p[b];
+        v[j] = x;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) s[j] = ld_slot(&t.slots[gs_hash(v[j]) & t.mask]);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (i0 + (uint32_t)j * stride >= total) continue;
+      if (v[j] != 0 && s[j] == v[j]) continue;
+      gs_insert(t, v[j]);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void k_gs_move(GsTable src, GsTable dst) {
   if (blockIdx.x == 0 && threadIdx.x == 0 && src.meta[kGsZero]) gs_insert(dst, 0);
   const uint32_t cap = src.mask + 1;
@@ -257,6 +370,27 @@ hipError_t launch_gs_insert_parts(hipStream_t s, GsTable t, const GsParts& ps) {
   if (ps.k == 0 || ps.pre[ps.k] == 0) return hipSuccess;
   // four elements per lane and round
   hipLaunchKernelGGL(k_gs_insert_parts, dim3(blocks_for((ps.pre[ps.k] + 3) / 4)), dim3(256), 0, s, t, ps);
+  return hipGetLastError();
+}
+
+hipError_t launch_gs_state_runs(hipStream_t s, const uint8_t* base, const GsStateFile* files, uint32_t n,
+                                uint32_t max_count, uint32_t* runs) {
+  if (n == 0) return hipSuccess;
+  // (t runs to the count inclusive; the grid's x covers the longest file, y the files)
+  const uint32_t gy = n < 64 ? n : 64;
+  uint32_t gx = blocks_for(max_count + 1);
+  if (gx > 4096 / gy) gx = 4096 / gy;
+  for (uint32_t phase = 0; phase < 5; phase++) {
+    hipLaunchKernelGGL(k_gs_state_runs, dim3(gx, gy), dim3(256), 0, s, base, files, n, runs, phase);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_gs_state_insert(hipStream_t s, GsTable t, const uint8_t* base, const GsStateFile* files, uint32_t k,
+                                  uint32_t total, const uint32_t* runs) {
+  if (k == 0 || total == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gs_state_insert, dim3(blocks_for((total + 3) / 4)), dim3(256), 0, s, t, base, files, k, runs);
   return hipGetLastError();
 }
 

@@ -35,6 +35,10 @@ struct GsState {
   DevBuf gate;      // the sharded gate's block: e0 u64[m] | newnov u64[m]
   DevBuf fused;     // GsFused: what the fused open reads through DecodeArgs.gs
   GsFused h_fused;  // its host copy (lives through the upload)
+  // the state-file reader: GsStateFile[n] | run words [kGsStateRunWords * n]
+  DevBuf rd;
+  HostBuf h_rd;                  // pinned: the heads' prefixes, the descriptors' upload, the run table
+  uint64_t head_hint = 1u << 14;  // state head prefix to download (gs_merge_states_device)
 };
 
 void gs_free(GsState* g) { delete g; }
@@ -250,6 +254,209 @@ int gs_insert_members(ce_core* c, const std::vector<uint64_t>& members) {
   return CE_OK;
 }
 
+namespace {
+
+// The head of a StateWrapper exactly as the writer leaves it: 82 b0"next_op_versions" <clock>
+// a5"state" 81 a5"value" <array header>.  0: found, *nov / *count / *body (the first element's
+// offset) set; 1: another shape (the host parser's); 2: the prefix ended inside the head.
+int parse_state_head(const uint8_t* p, uint64_t n, bool whole, Dots* nov, uint64_t* count, uint64_t* body) {
+  Rd r{p, n, 0};
+  const int cut = whole ? 1 : 2;
+  auto lit = [&](const char* s, uint64_t l) -> int {
+    const uint64_t have = std::min<uint64_t>(l, r.n - r.i);
+    if (std::memcmp(r.p + r.i, s, have) != 0) return 1;
+    if (have < l) return cut;
+    r.i += l;
+    return 0;
+  };
+  if (int x = lit("\x82\xb0next_op_versions", 18)) return x;
+  nov->clear();
+  if (!read_vclock(r, nov)) return cut;
+  if (int x = lit("\xa5state\x81\xa5value", 13)) return x;
+  if (r.i < r.n && !is_array_marker(r.p[r.i])) return 1;
+  if (!rd_array_hdr(r, count)) return cut;
+  *body = r.i;
+  return 0;
+}
+
+bool read_gset_wrapper(const uint8_t* p, size_t n, Dots* nov, std::vector<uint64_t>* members) {
+  Rd r{p, n, 0};
+  return read_struct(r, {"next_op_versions", "state"},
+                     [&](int f, Rd& q) { return f == 0 ? read_vclock(q, nov) : read_gset_state(q, members); });
+}
+
+constexpr uint32_t kRunWidth[5] = {1, 2, 3, 5, 9};
+
+}  // namespace
+
+// files i = StateWrapper plaintexts at base + off[i], len[i] bytes, st[i] = status so far.  The
+// heads are parsed on the host from a prefix; a body whose element widths never decrease is proven
+// on the device (k_gs_state_runs) and inserted from HBM (k_gs_state_insert); every other file is
+// downloaded whole for the host parser, whose verdict it keeps.  Nothing is inserted before every
+// file has its status.  Host waits: the heads, the run table, the inserts' end (which reads the
+// table's counts: a launch that met the load bound costs a rehash and a second pass).
+int gs_merge_states_device(ce_core* c, const uint8_t* base, const std::vector<uint64_t>& off,
+                           const std::vector<uint64_t>& len, int32_t* st, int32_t* status_out) {
+  ce_ctx* ctx = c->ctx;
+  GsState* g = c->gs;
+  hipStream_t s = ctx->stream;
+  const size_t n = off.size();
+  hipError_t e;
+  int rc;
+  std::vector<Dots> novs(n);
+  std::vector<uint64_t> host_members;
+  std::vector<uint8_t> whole;
+  uint64_t n_dev = 0, n_host = 0;  // (counted when the call has taken its files)
+  auto host_parse = [&](size_t i) -> int {  // the whole plaintext through the host parser
+    n_host++;
+    whole.resize(len[i]);
+    if (len[i] && ((e = hipMemcpyAsync(whole.data(), base + off[i], len[i], hipMemcpyDeviceToHost, s)) ||
+                   (e = stream_wait(s))))
+      return ctx->hip_fail(e, "state download");
+    novs[i].clear();
+    if (!read_gset_wrapper(whole.data(), len[i], &novs[i], &host_members)) st[i] = CE_ERR_DECODE;
+    return CE_OK;
+  };
+  // 1) the heads: one prefix per file into pinned memory, one wait
+  const uint64_t hint = g->head_hint;
+  std::vector<uint64_t> poff(n + 1, 0);
+  for (size_t i = 0; i < n; i++) poff[i + 1] = poff[i] + (st[i] == CE_OK ? std::min<uint64_t>(len[i], hint) : 0);
+  const uint64_t files_at = (poff[n] + 63) & ~63ull;
+  const uint64_t runs_at = files_at + sizeof(GsStateFile) * n;
+  const uint64_t table_bytes = 4ull * kGsStateRunWords * n;
+  const uint64_t meta_at = runs_at + table_bytes;  // the committed table's counts before the inserts
+  if ((e = g->h_rd.reserve(meta_at + 4ull * kMetaWords + 64)) ||
+      (e = g->rd.reserve(sizeof(GsStateFile) * n + table_bytes + 64)))
+    return ctx->hip_fail(e, "state reader");
+  uint8_t* hb = g->h_rd.as<uint8_t>();
+  for (size_t i = 0; i < n; i++)
+    if (poff[i + 1] > poff[i] &&
+        (e = hipMemcpyAsync(hb + poff[i], base + off[i], poff[i + 1] - poff[i], hipMemcpyDeviceToHost, s)))
+      return ctx->hip_fail(e, "state head");
+  if ((e = stream_wait(s))) return ctx->hip_fail(e, "state head");
+  GsStateFile* hf = reinterpret_cast<GsStateFile*>(hb + files_at);
+  std::vector<size_t> dev;  // the files the device reads, in descriptor order
+  uint64_t head_max = 0;
+  uint32_t max_count = 0;
+  std::vector<uint8_t> pre;
+  for (size_t i = 0; i < n; i++) {
+    if (st[i] != CE_OK) continue;
+    uint64_t want = poff[i + 1] - poff[i], count = 0, body = 0;
+    int pr = parse_state_head(hb + poff[i], want, want == len[i], &novs[i], &count, &body);
+    if (pr == 2) {  // a longer head: once more with a larger prefix
+      want = std::min<uint64_t>(len[i], want * 16);
+      pre.resize(want);
+      if ((e = hipMemcpyAsync(pre.data(), base + off[i], want, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+        return ctx->hip_fail(e, "state head");
+      pr = parse_state_head(pre.data(), want, want == len[i], &novs[i], &count, &body);
+    }
+    const uint64_t blen = len[i] - body;
+    // (32-bit element offsets: 9 count < 2^32; a count above the bytes left is the host's to refuse)
+    if (pr != 0 || blen > 0xffffffffull || 9 * count >= (1ull << 32)) {
+      if ((rc = host_parse(i))) return rc;
+      continue;
+    }
+    head_max = std::max(head_max, body);
+    hf[dev.size()] = GsStateFile{off[i] + body, (uint32_t)blen, (uint32_t)count, 0, 0};
+    max_count = std::max(max_count, (uint32_t)count);
+    dev.push_back(i);
+  }
+  if (head_max) {
+    uint64_t h = 1u << 14;
+    while (h < head_max + head_max / 4 + 64 && h < (1u << 18)) h <<= 1;
+    g->head_hint = h;
+  }
+  // 2) the runs: five phases over every device file, back to back; the run table comes back in
+  //    one download
+  const uint32_t nd = (uint32_t)dev.size();
+  GsStateFile* d_files = g->rd.as<GsStateFile>();
+  uint32_t* d_runs = reinterpret_cast<uint32_t*>(g->rd.as<uint8_t>() + sizeof(GsStateFile) * n);
+  const uint32_t* hr = reinterpret_cast<const uint32_t*>(hb + runs_at);
+  if (nd) {
+    if ((e = hipMemcpyAsync(d_files, hf, sizeof(GsStateFile) * nd, hipMemcpyHostToDevice, s)) ||
+        (e = hipMemsetAsync(d_runs, 0xff, 4ull * kGsStateRunWords * nd, s)))
+      return ctx->hip_fail(e, "state reader");
+    const int t = ctx->tbegin("gset_state_runs");
+    if ((e = launch_gs_state_runs(s, base, d_files, nd, max_count, d_runs))) return ctx->hip_fail(e, "state reader");
+    ctx->tend(t);
+    if ((e = hipMemcpyAsync(hb + runs_at, d_runs, 4ull * kGsStateRunWords * nd, hipMemcpyDeviceToHost, s)) ||
+        (e = hipMemcpyAsync(hb + meta_at, g->meta.p, 4ull * kMetaWords, hipMemcpyDeviceToHost, s)) ||
+        (e = stream_wait(s)))
+      return ctx->hip_fail(e, "state reader");
+  }
+  // a file whose runs sum to its count is proven, element by element; any other is the host's
+  uint64_t dev_members = 0, max_proven = 0;
+  for (uint32_t k = 0; k < nd; k++) {
+    const uint32_t* R = hr + kGsStateRunWords * k;
+    uint64_t sum = 0, end = 0;
+    for (int r = 0; r < 5; r++) {
+      sum += R[r];
+      end += (uint64_t)R[r] * kRunWidth[r];
+    }
+    if (sum == hf[k].count && end <= hf[k].blen && dev_members + sum <= (1ull << 30)) {
+      dev_members += sum;
+      max_proven = std::max(max_proven, sum);
+      n_dev++;
+      continue;
+    }
+    hf[k].count = 0;  // (skipped by the insert)
+    if ((rc = host_parse(dev[k]))) return rc;
+  }
+  // 3) every file has its status: all or nothing (lib.rs:425-466)
+  if (status_out) std::memcpy(status_out, st, n * 4ull);
+  for (size_t i = 0; i < n; i++)
+    if (st[i] != CE_OK) return ctx->fail(st[i], st[i] == CE_ERR_DECODE ? "not a StateWrapper" : "state file rejected");
+  // 4) the members: the proven files in launches of kGsStateMaxFiles, then the host-parsed ones
+  // (a table that cannot hold even the largest file's members is grown ahead: a new replica's
+  // first compaction would otherwise pay a pass that is certain to meet the load bound)
+  if (dev_members && max_proven > g->cap / 2 &&
+      (rc = ensure_committed(c, reinterpret_cast<const uint32_t*>(hb + meta_at)[kGsCount], dev_members)))
+    return rc;
+  for (int pass = 0; dev_members; pass++) {
+    for (uint32_t k0 = 0; k0 < nd; k0 += kGsStateMaxFiles) {
+      const uint32_t k = std::min(kGsStateMaxFiles, nd - k0);
+      uint32_t total = 0;
+      for (uint32_t j = 0; j < k; j++) {
+        hf[k0 + j].pre = total;
+        total += hf[k0 + j].count;
+      }
+      if (total == 0) continue;
+      if (pass == 0 &&
+          (e = hipMemcpyAsync(d_files + k0, hf + k0, sizeof(GsStateFile) * k, hipMemcpyHostToDevice, s)))
+        return ctx->hip_fail(e, "state insert");
+      const int t = ctx->tbegin("gset_state_insert");
+      if ((e = launch_gs_state_insert(s, committed(g), base, d_files + k0, k, total, d_runs + kGsStateRunWords * k0)))
+        return ctx->hip_fail(e, "state insert");
+      ctx->tend(t);
+    }
+    // The table is not grown ahead for members it may already hold (a compaction mostly repeats
+    // the one before it).  The wait that ends the call reads its counts back: a launch that met
+    // the load bound is run once more (inserts are idempotent) after one growth, to room for
+    // the members the table held before the call (read with the run table) and every member of
+    // the call.
+    uint32_t now[kMetaWords];
+    if ((rc = read_meta(c, now))) return rc;
+    if (!now[kGsOverflow]) break;
+    if (pass) return ctx->fail(CE_ERR_DEVICE, "committed table did not take the state files");
+    const uint32_t before = reinterpret_cast<const uint32_t*>(hb + meta_at)[kGsCount];
+    if ((e = hipMemsetAsync(g->meta.as<uint32_t>() + kGsOverflow, 0, 4, s))) return ctx->hip_fail(e, "gset grow");
+    if ((rc = ensure_committed(c, before, dev_members))) return rc;
+  }
+  if ((rc = gs_insert_members(c, host_members))) return rc;
+  // state.merge done; next_op_versions.merge(sw.next_op_versions) (lib.rs:461-463)
+  for (size_t i = 0; i < n; i++)
+    for (auto& d : novs[i]) {
+      uint32_t slot;
+      if ((rc = insert_actor(c, d.first, &slot))) return rc;
+      c->nov[slot] = std::max(c->nov[slot], d.second);
+    }
+  if ((rc = table_upload(c))) return rc;
+  // (the plaintexts may be the caller's buffer: the inserts have been waited for above)
+  c->path_counts["gset_states_device_read"] += n_dev;
+  c->path_counts["gset_states_host_read"] += n_host;
+  return CE_OK;
+}
+
 // the set in BTreeSet order in g->sorted (device): the live slots collected, then the radix sort
 // (ce_ser_sort.hip's generic u64 key mode); *n_out = the member count
 static int collect_sorted(ce_core* c, uint32_t* n_members) {
@@ -367,6 +574,36 @@ int gs_serialize_device(ce_core* c, std::vector<uint8_t> head, std::vector<uint8
   if (clear_len && ((e = hipMemcpyAsync(out->data(), db, clear_len, hipMemcpyDeviceToHost, ctx->stream)) ||
                     (e = stream_wait(ctx->stream))))
     return ctx->hip_fail(e, "gset state bytes");
+  return CE_OK;
+}
+
+// ce_core_state_bytes into device memory: the writer's clear text stays in HBM, only its length
+// comes to the host
+int gs_state_bytes_device(ce_core* c, std::vector<uint8_t> head, uint8_t* d_dst, uint64_t cap, uint64_t* len) {
+  ce_ctx* ctx = c->ctx;
+  uint64_t A = 0, U = 0, clear_len = 0;
+  int rc;
+  {
+    HostPhase hp("gset bytes: write");
+    if ((rc = write_device(c, std::move(head), nullptr, nullptr, &A, &U))) return rc;
+  }
+  const uint8_t* db = ctx->blob.as<uint8_t>();
+  hipError_t e;
+  {
+    HostPhase hp("gset bytes: length");
+    if ((e = hipMemcpyAsync(&clear_len, db + A + 8, 8, hipMemcpyDeviceToHost, ctx->stream)) ||
+        (e = stream_wait(ctx->stream)))
+      return ctx->hip_fail(e, "gset state bytes");
+  }
+  if (clear_len > U) return ctx->fail(CE_ERR_DEVICE, "serialized state past its bound");
+  *len = clear_len;
+  if (clear_len > cap) return ctx->fail(CE_ERR_INVALID_ARG, "device buffer too small for the state");
+  // complete on return: the caller's collective may run on another stream
+  HostPhase hp("gset bytes: copy");
+  if (clear_len && ((e = hipMemcpyAsync(d_dst, db, clear_len, hipMemcpyDeviceToDevice, ctx->stream)) ||
+                    (e = stream_wait(ctx->stream))))
+    return ctx->hip_fail(e, "gset state bytes");
+  c->path_counts["gset_state_bytes_device"]++;
   return CE_OK;
 }
 

@@ -226,7 +226,12 @@ enum ce_state_kind {
                             (CE_HOST_COMPACT=1: encoded by the host writer, the cross-check).
                             ce_core_path_count keys: gset_fused_files (decoded inside the fused
                             open), gset_uniform_files, gset_general_files, gset_refolds,
-                            gset_grows, gset_batch_grows, gset_device_writes.                    */
+                            gset_grows, gset_batch_grows, gset_device_writes,
+                            gset_states_device_read (state files decoded in HBM),
+                            gset_states_host_read (state files the host parser took;
+                            CE_HOST_STATES=1: every state file, uncounted),
+                            gset_state_bytes_device (ce_core_state_bytes_device calls whose
+                            bytes never left HBM).                                              */
 };
 
 enum ce_open_flags {
