@@ -63,6 +63,9 @@ EXPORTS = [
     "ce_core_merge_columns_device", "ce_core_ingest_states_device",
     "ce_core_compact_into_async", "ce_core_compact_wait", "ce_host_alloc", "ce_host_free", "ce_content_names",
     "ce_core_gset_ingest_ops_device_sharded", "ce_core_gset_pending_members", "ce_core_gset_pending_commit",
+    "ce_core_set_contains_device", "ce_core_set_contains", "ce_core_set_len", "ce_core_set_members_device",
+    "ce_core_counter_read", "ce_core_clock_get", "ce_core_read_clock", "ce_core_orswot_member_clocks",
+    "ce_core_mvreg_read",
 ]
 
 
@@ -156,6 +159,46 @@ def shard_window_exact(e0, file_actor, file_version):
     if rc:
         raise CeError(rc, "ce_shard_window_exact")
     return hi[:m], int(hi[m])
+
+
+# ---- the with_state reads' buffers (include/crdtenc.h, ce_core_read_clock and after) ----
+def decode_clock(buf):
+    """ce_core_read_clock's bytes -> [(actor uuid bytes, counter)]: 24-byte entries (uuid16, u64
+    LE), in the order they were written (ascending UUID bytes)."""
+    import struct
+    if len(buf) % 24:
+        raise ValueError("clock buffer of %d bytes is not a whole number of 24-byte entries" % len(buf))
+    return [(bytes(buf[o:o + 16]), struct.unpack_from("<Q", buf, o + 16)[0]) for o in range(0, len(buf), 24)]
+
+
+def decode_member_clocks(buf, n):
+    """ce_core_orswot_member_clocks' bytes for n queried members -> n lists of (actor uuid bytes,
+    counter): u32 beg[n + 1], padded to 8 bytes, then 24-byte entries; member i's are
+    [beg[i], beg[i + 1]) (empty for an absent member)."""
+    import struct
+    head = ((n + 1) * 4 + 7) & ~7
+    if len(buf) < head:
+        raise ValueError("member-clock buffer shorter than its %d offsets" % (n + 1))
+    beg = struct.unpack_from("<%dI" % (n + 1), buf, 0)
+    if beg[0] != 0 or any(beg[i] > beg[i + 1] for i in range(n)) or len(buf) != head + 24 * beg[n]:
+        raise ValueError("member-clock offsets do not describe the buffer")
+    ent = decode_clock(buf[head:])
+    return [ent[beg[i]:beg[i + 1]] for i in range(n)]
+
+
+def pn_words(p, n):
+    """(mag_lo, mag_hi, negative) of p - n for two sums below 2^128: what ce_core_counter_read
+    returns for a PNCounter whose planes sum to p and n (n = 0: a GCounter)."""
+    if not (0 <= p < 1 << 128 and 0 <= n < 1 << 128):
+        raise ValueError("sums are 128-bit")
+    m = p - n if p >= n else n - p
+    return m & 0xFFFFFFFFFFFFFFFF, m >> 64, 1 if p < n else 0
+
+
+def counter_int(mag_lo, mag_hi, negative):
+    """ce_core_counter_read's words -> the Python int GCounter::read / PNCounter::read give"""
+    m = (int(mag_hi) << 64) | int(mag_lo)
+    return -m if negative else m
 
 
 class CeError(RuntimeError):
@@ -990,6 +1033,75 @@ class Core:
         cs = (ctypes.c_uint64 * max(k, 1))(*counts)
         return lib().ce_core_gset_pending_commit(self.p, 1 if accept else 0, ptrs if k else None,
                                                  cs if k else None, ctypes.c_uint32(k))
+
+    # ---- with_state reads (lib.rs:325-330): the committed state answered from HBM ----
+    def contains_device(self, d_members, n, d_out):
+        """d_out[i] = 1 if d_members[i] is in the set else 0 (device pointers: u64[n], u8[n]);
+        Orswot and GSet.  Returns the status."""
+        return lib().ce_core_set_contains_device(self.p, ctypes.c_void_p(d_members) if d_members else None,
+                                                 ctypes.c_uint64(n), ctypes.c_void_p(d_out) if d_out else None)
+
+    def contains(self, members):
+        """numpy u8[len(members)]: 1 where the member is in the set (host buffers)."""
+        import numpy as np
+        q, qp = _np_ptr(members, np.uint64)
+        out = np.zeros(len(q), np.uint8)
+        self.ctx.check(lib().ce_core_set_contains(self.p, qp if len(q) else None, ctypes.c_uint64(len(q)),
+                                                  ctypes.c_void_p(out.ctypes.data) if len(q) else None), "contains")
+        return out
+
+    def set_len(self):
+        n = ctypes.c_uint64(0)
+        self.ctx.check(lib().ce_core_set_len(self.p, ctypes.byref(n)), "set_len")
+        return n.value
+
+    def members_device(self, d_dst, cap):
+        """The members ascending into d_dst (device u64[cap]): (rc, n); n is always the member
+        count, and nothing is written when cap < n."""
+        n = ctypes.c_uint64(0)
+        rc = lib().ce_core_set_members_device(self.p, ctypes.c_void_p(d_dst) if d_dst else None,
+                                              ctypes.c_uint64(cap), ctypes.byref(n))
+        return rc, n.value
+
+    def counter_read(self):
+        """GCounter::read / PNCounter::read as a Python int."""
+        mag = (ctypes.c_uint64 * 2)()
+        neg = ctypes.c_int(0)
+        self.ctx.check(lib().ce_core_counter_read(self.p, mag, ctypes.byref(neg)), "counter_read")
+        return counter_int(mag[0], mag[1], neg.value)
+
+    def clock_get(self, actors, which=0):
+        """VClock::get for each actor (list of 16-byte ids): list of ints, 0 for an unknown one.
+        which = 1: a PNCounter's n."""
+        m = len(actors)
+        out = (ctypes.c_uint64 * max(m, 1))()
+        self.ctx.check(lib().ce_core_clock_get(self.p, ctypes.c_int(which), _cbuf(b"".join(actors)) if m else None,
+                                               ctypes.c_uint32(m), out if m else None), "clock_get")
+        return list(out)[:m]
+
+    def read_clock(self, which=0):
+        """The clock whole: [(actor uuid bytes, counter)], counters > 0, ascending by UUID bytes."""
+        b = Buf()
+        self.ctx.check(lib().ce_core_read_clock(self.p, ctypes.c_int(which), ctypes.byref(b)), "read_clock")
+        return decode_clock(_take(b))
+
+    def orswot_member_clocks(self, members):
+        """Orswot::contains(m).rm_clock per queried member: a list of [(actor, counter)] lists in
+        query order (empty for an absent member)."""
+        import numpy as np
+        q, qp = _np_ptr(members, np.uint64)
+        b = Buf()
+        self.ctx.check(lib().ce_core_orswot_member_clocks(self.p, qp if len(q) else None, ctypes.c_uint32(len(q)),
+                                                          ctypes.byref(b)), "orswot_member_clocks")
+        return decode_member_clocks(_take(b), len(q))
+
+    def mvreg_read(self):
+        """MVReg::read().val: the values in the order state_bytes writes them."""
+        import struct
+        b = Buf()
+        self.ctx.check(lib().ce_core_mvreg_read(self.p, ctypes.byref(b)), "mvreg_read")
+        d = _take(b)
+        return list(struct.unpack("<%dQ" % (len(d) // 8), d))
 
     def writer_versions(self, actors):
         import numpy as np

@@ -2402,6 +2402,205 @@ int ce_core_merge_columns_device(ce_core* c, const uint8_t* const* d_parts, cons
   return ds_merge_columns_device(c, d_parts, lens, k);
 }
 
+// ---------------------------------------------------------------------------------------
+// with_state reads (lib.rs:325-330): the committed state answered from HBM.  Every call takes
+// the context lock, selects the device, and settles a fold or merge queued without a host wait
+// (ds_settle / gs_settle; the dense kinds' reads are ordered behind it on the stream).  A kind the
+// call does not serve: CE_ERR_INVALID_ARG before any output is touched.
+// ---------------------------------------------------------------------------------------
+static bool is_set_kind(int kind) { return kind == CE_STATE_ORSWOT || kind == CE_STATE_GSET; }
+static bool has_counter(int kind) { return kind == CE_STATE_GCOUNTER || kind == CE_STATE_PNCOUNTER; }
+// `which` names a clock of the kind: 0 for every kind but GSet, 1 (the n plane) for PNCounter
+static bool has_clock(int kind, int which) {
+  return kind != CE_STATE_GSET && (which == 0 || (which == 1 && kind == CE_STATE_PNCOUNTER));
+}
+
+static void fill_buf(ce_buf* out, const void* p, size_t n) {
+  out->data = (uint8_t*)malloc(n ? n : 1);
+  if (n) std::memcpy(out->data, p, n);
+  out->len = n;
+}
+
+// (uuid16, u64 LE counter) entries ascending by UUID bytes
+static void write_clock_entries(Dots* d, std::vector<uint8_t>* b) {
+  std::sort(d->begin(), d->end());
+  b->resize(24 * d->size());
+  uint8_t* p = b->data();
+  for (auto& x : *d) {
+    std::memcpy(p, x.first.data(), 16);
+    std::memcpy(p + 16, &x.second, 8);
+    p += 24;
+  }
+}
+
+int ce_core_set_contains_device(ce_core* c, const uint64_t* d_members, uint64_t n, uint8_t* d_out) {
+  if (!c || (n && (!d_members || !d_out))) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  if (!is_set_kind(c->kind)) return c->ctx->fail(CE_ERR_INVALID_ARG, "contains: not a set kind");
+  if (c->kind == CE_STATE_ORSWOT) return ds_contains_device(c, d_members, n, d_out);
+  int rc = gs_settle(c);
+  return rc ? rc : gs_contains_device(c, d_members, n, d_out);
+}
+
+int ce_core_set_contains(ce_core* c, const uint64_t* members, uint64_t n, uint8_t* out) {
+  if (!c || (n && (!members || !out))) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  ce_ctx* ctx = c->ctx;
+  if (!is_set_kind(c->kind)) return ctx->fail(CE_ERR_INVALID_ARG, "contains: not a set kind");
+  hipError_t e;
+  if (n && ((e = c->d_rq.reserve(n * 8 + 64)) || (e = c->d_ra.reserve(n + 64)) ||
+            (e = hipMemcpyAsync(c->d_rq.p, members, n * 8, hipMemcpyHostToDevice, ctx->stream))))
+    return ctx->hip_fail(e, "contains upload");
+  int rc = ce_core_set_contains_device(c, c->d_rq.as<uint64_t>(), n, c->d_ra.as<uint8_t>());
+  if (rc || n == 0) return rc;
+  if ((e = hipMemcpyAsync(out, c->d_ra.p, n, hipMemcpyDeviceToHost, ctx->stream)) || (e = stream_wait(ctx->stream)))
+    return ctx->hip_fail(e, "contains download");
+  return CE_OK;
+}
+
+int ce_core_set_len(ce_core* c, uint64_t* n) {
+  if (!c || !n) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  if (!is_set_kind(c->kind)) return c->ctx->fail(CE_ERR_INVALID_ARG, "len: not a set kind");
+  uint64_t v = 0;
+  int rc = c->kind == CE_STATE_ORSWOT ? ds_set_len(c, &v) : gs_settle(c);
+  if (rc == CE_OK && c->kind == CE_STATE_GSET) rc = gs_set_len(c, &v);
+  if (rc == CE_OK) *n = v;
+  return rc;
+}
+
+int ce_core_set_members_device(ce_core* c, uint64_t* d_dst, uint64_t cap, uint64_t* n) {
+  if (!c || !n || (cap && !d_dst)) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  if (!is_set_kind(c->kind)) return c->ctx->fail(CE_ERR_INVALID_ARG, "members: not a set kind");
+  uint64_t v = 0;
+  int rc = c->kind == CE_STATE_ORSWOT ? ds_members_device(c, d_dst, cap, &v) : gs_settle(c);
+  if (rc == CE_OK && c->kind == CE_STATE_GSET) rc = gs_members_device(c, d_dst, cap, &v);
+  if (rc == CE_OK) *n = v;
+  return rc;
+}
+
+int ce_core_counter_read(ce_core* c, uint64_t mag[2], int* negative) {
+  if (!c || !mag || !negative) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  ce_ctx* ctx = c->ctx;
+  if (!has_counter(c->kind)) return ctx->fail(CE_ERR_INVALID_ARG, "counter_read: not a counter kind");
+  const uint32_t planes = state_planes(c->kind);
+  hipError_t e;
+  if ((e = c->d_rsum.reserve(64)) || (e = c->h_read.reserve(64)) || (e = hipMemsetAsync(c->d_rsum.p, 0, 32, ctx->stream)))
+    return ctx->hip_fail(e, "counter read");
+  const int t = ctx->tbegin("sum_u64_128");
+  if ((e = launch_sum_u64_128(ctx->stream, c->d_state.as<unsigned long long>(), c->cap, planes,
+                              c->d_rsum.as<unsigned long long>())))
+    return ctx->hip_fail(e, "counter read");
+  ctx->tend(t);
+  if ((e = hipMemcpyAsync(c->h_read.p, c->d_rsum.p, 32, hipMemcpyDeviceToHost, ctx->stream)) ||
+      (e = stream_wait(ctx->stream)))
+    return ctx->hip_fail(e, "counter read");
+  const uint64_t* s = c->h_read.as<uint64_t>();  // p low, p high, n low, n high (n: PNCounter)
+  const unsigned __int128 p = ((unsigned __int128)s[1] << 64) | s[0];
+  const unsigned __int128 q = planes == 2 ? ((unsigned __int128)s[3] << 64) | s[2] : 0;
+  const unsigned __int128 m = p >= q ? p - q : q - p;
+  mag[0] = (uint64_t)m;
+  mag[1] = (uint64_t)(m >> 64);
+  *negative = p < q ? 1 : 0;
+  return CE_OK;
+}
+
+int ce_core_clock_get(ce_core* c, int which, const uint8_t* actors, uint32_t m, uint64_t* out) {
+  if (!c || (m && (!actors || !out))) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  ce_ctx* ctx = c->ctx;
+  if (!has_clock(c->kind, which)) return ctx->fail(CE_ERR_INVALID_ARG, "clock_get: no such clock for this kind");
+  if (is_dotset_kind(c->kind)) {
+    Dots clock;
+    int rc = ds_read_clock(c, &clock);
+    if (rc) return rc;
+    std::unordered_map<Uuid, uint64_t, UuidHash> by;
+    for (auto& x : clock) by[x.first] = x.second;
+    for (uint32_t i = 0; i < m; i++) {
+      Uuid u;
+      std::memcpy(u.data(), actors + 16ull * i, 16);
+      auto it = by.find(u);
+      out[i] = it == by.end() ? 0 : it->second;
+    }
+    return CE_OK;
+  }
+  if (m == 0) return CE_OK;
+  // slots on the host, the counters gathered by one kernel and brought back by one copy
+  hipError_t e;
+  if ((e = c->h_read.reserve(12ull * m + 64)) || (e = c->d_rq.reserve(4ull * m + 64)) || (e = c->d_ra.reserve(8ull * m + 64)))
+    return ctx->hip_fail(e, "clock get");
+  uint64_t* hv = c->h_read.as<uint64_t>();
+  uint32_t* hi = reinterpret_cast<uint32_t*>(hv + m);
+  for (uint32_t i = 0; i < m; i++) {
+    Uuid u;
+    std::memcpy(u.data(), actors + 16ull * i, 16);
+    auto it = c->slot_of.find(u);
+    hi[i] = it == c->slot_of.end() ? 0xffffffffu : it->second + (which ? c->cap : 0u);
+  }
+  if ((e = hipMemcpyAsync(c->d_rq.p, hi, 4ull * m, hipMemcpyHostToDevice, ctx->stream)) ||
+      (e = launch_gather_u64(ctx->stream, c->d_state.as<unsigned long long>(), c->d_rq.as<uint32_t>(), m,
+                             c->d_ra.as<unsigned long long>())) ||
+      (e = hipMemcpyAsync(hv, c->d_ra.p, 8ull * m, hipMemcpyDeviceToHost, ctx->stream)) ||
+      (e = stream_wait(ctx->stream)))
+    return ctx->hip_fail(e, "clock get");
+  std::memcpy(out, hv, 8ull * m);
+  return CE_OK;
+}
+
+int ce_core_read_clock(ce_core* c, int which, ce_buf* out) {
+  if (!c || !out) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  if (!has_clock(c->kind, which)) return c->ctx->fail(CE_ERR_INVALID_ARG, "read_clock: no such clock for this kind");
+  Dots clock;
+  int rc;
+  if (is_dotset_kind(c->kind)) {
+    if ((rc = ds_read_clock(c, &clock))) return rc;
+  } else {
+    std::vector<uint64_t> st;
+    if ((rc = download_state(c, &st))) return rc;
+    const uint64_t* plane = st.data() + (which ? c->cap : 0u);
+    for (uint32_t s = 0; s < c->cap; s++)
+      if (c->h_table[s].used && plane[s]) clock.push_back({c->slot_actor[s], plane[s]});
+  }
+  std::vector<uint8_t> b;
+  write_clock_entries(&clock, &b);
+  fill_buf(out, b.data(), b.size());
+  return CE_OK;
+}
+
+int ce_core_orswot_member_clocks(ce_core* c, const uint64_t* members, uint32_t n, ce_buf* out) {
+  if (!c || !out || (n && !members)) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  if (c->kind != CE_STATE_ORSWOT) return c->ctx->fail(CE_ERR_INVALID_ARG, "member clocks: not an Orswot");
+  std::vector<uint8_t> b;
+  int rc = ds_member_clocks(c, members, n, &b);
+  if (rc) return rc;
+  fill_buf(out, b.data(), b.size());
+  return CE_OK;
+}
+
+int ce_core_mvreg_read(ce_core* c, ce_buf* out) {
+  if (!c || !out) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  if (c->kind != CE_STATE_MVREG) return c->ctx->fail(CE_ERR_INVALID_ARG, "mvreg_read: not an MVReg");
+  std::vector<uint64_t> v;
+  int rc = ds_mvreg_read(c, &v);
+  if (rc) return rc;
+  fill_buf(out, v.data(), v.size() * 8);
+  return CE_OK;
+}
+
 void* ce_host_alloc(size_t bytes) {
   void* p = nullptr;
   return hipHostMalloc(&p, bytes ? bytes : 1, 0) == hipSuccess ? p : nullptr;

@@ -133,6 +133,10 @@ struct ce_core {
   ce::HostBuf h_shard;                 // pinned staging of the e0 upload (its own: the copy is async)
   std::vector<uint64_t> shard_e0;      // the e0 d_shard holds
   std::vector<uint8_t> shard_writers;  // the writer list d_shard holds
+  // with_state reads: the host-buffer forms' query / answer columns, the dense kinds' sums and
+  // gather indices (device), and the pinned block their small results land in
+  ce::DevBuf d_rq, d_ra, d_rsum;
+  ce::HostBuf h_read;
 };
 
 namespace ce {
@@ -265,6 +269,17 @@ int ds_settle(ce_core* c);
 int ds_state_bytes_device(ce_core* c, ce_ctx* x, uint8_t* dst, uint64_t cap, uint64_t* len);
 int ds_export_columns_device(ce_core* c, uint8_t* dst, uint64_t cap, uint64_t* len);
 int ds_merge_columns_device(ce_core* c, const uint8_t* const* parts, const uint64_t* lens, uint32_t k);
+// with_state reads (lib.rs:325-330), each after ds_settle.  Orswot: contains / len / members from
+// the per-handle live flags (rebuilt when the tables changed since), entries[m] per queried member
+// (u32 beg[n + 1], padded to 8 bytes, then 24-byte (uuid, u64 LE) entries in UUID order).  Orswot
+// and MVReg: the clock / the join of the values' clocks, counters > 0, in no order.  MVReg: the
+// values in ds_serialize's order.
+int ds_contains_device(ce_core* c, const uint64_t* d_members, uint64_t n, uint8_t* d_out);
+int ds_set_len(ce_core* c, uint64_t* n);
+int ds_members_device(ce_core* c, uint64_t* d_dst, uint64_t cap, uint64_t* n);
+int ds_read_clock(ce_core* c, Dots* out);
+int ds_member_clocks(ce_core* c, const uint64_t* members, uint32_t n, std::vector<uint8_t>* out);
+int ds_mvreg_read(ce_core* c, std::vector<uint64_t>* out);
 // Core::apply_ops for a local Vec<S::Op> (already validated by ds_check_ops)
 int ds_check_ops(ce_core* c, const uint8_t* ops, size_t len);
 int ds_apply_local_ops(ce_core* c, const uint8_t* ops, size_t len);
@@ -296,6 +311,12 @@ int gs_state_bytes_device(ce_core* c, std::vector<uint8_t> head, uint8_t* d_dst,
 // device, every other file through the host parser; all or nothing
 int gs_merge_states_device(ce_core* c, const uint8_t* base, const std::vector<uint64_t>& off,
                            const std::vector<uint64_t>& len, int32_t* st, int32_t* status_out);
+// with_state reads (lib.rs:325-330) of the committed table (a pending sharded batch is no part of
+// them): contains over a query column in HBM, the member count, the members ascending in HBM
+// (*n always the count; nothing written when cap < *n)
+int gs_contains_device(ce_core* c, const uint64_t* d_members, uint64_t n, uint8_t* d_out);
+int gs_set_len(ce_core* c, uint64_t* n);
+int gs_members_device(ce_core* c, uint64_t* d_dst, uint64_t cap, uint64_t* n);
 // Vec<u64> as rmp-serde reads it (any non-negative integer form); false: CE_ERR_DECODE
 bool parse_gset_ops(const uint8_t* p, size_t n, std::vector<uint64_t>* out);
 // GSet { value: BTreeSet<u64> }: the reader (any order, duplicates) and the canonical writer

@@ -282,6 +282,25 @@ hipError_t launch_ds_gather_entries(hipStream_t s, const uint32_t* perm, const u
                                     const unsigned long long* value_in, uint32_t* actor_out,
                                     unsigned long long* value_out, uint32_t n);
 
+// The with_state reads of an Orswot.  flags: one byte per member slot, ms + pcap + 1 of them
+// (DsTables.smask + mmask + 3), 1 where some pair of the handle is live.
+// flags (zeroed beforehand) from one scan of the pair table
+hipError_t launch_ds_member_live(hipStream_t s, DsTables t, uint8_t* flags);
+// out[i] = Orswot::contains(q[i]).val for i < n (k_ds_contains: several probes in flight per lane;
+// grid_cap: the most blocks, 0 = 2048)
+hipError_t launch_ds_contains(hipStream_t s, DsTables t, const uint8_t* flags, const unsigned long long* q, uint64_t n,
+                              uint8_t* out, uint32_t grid_cap);
+// *out (zeroed beforehand) += the flags set among n
+hipError_t launch_ds_live_count(hipStream_t s, const uint8_t* flags, uint64_t n, uint32_t* out);
+// the flagged handles' members into out, in no order; *n_out (zeroed beforehand) = their count
+hipError_t launch_ds_live_members(hipStream_t s, DsTables t, const uint8_t* flags, unsigned long long* out,
+                                  uint32_t* n_out);
+// the live pairs of n distinct queried members: out[2 k] = query index << 32 | actor id, out[2 k + 1]
+// = the counter, in no order; *n_out (zeroed beforehand) = the pairs found, of which the first cap
+// were written.  qidx: a word per member slot, zeroed beforehand; mark = false: qidx is still marked
+hipError_t launch_ds_member_clocks(hipStream_t s, DsTables t, const unsigned long long* q, uint32_t n, uint32_t* qidx,
+                                   unsigned long long* out, uint32_t cap, uint32_t* n_out, bool mark);
+
 // device-wide primitives (sorts: ce_ser_sort.hip; scans: ce_scan.hip): tmp = nullptr queries the temp
 // size into tb
 hipError_t ds_sort_pairs_u32(void* tmp, size_t& tb, const uint32_t* kin, uint32_t* kout,

@@ -2322,6 +2322,143 @@ hipError_t launch_ds_gather_entries(hipStream_t s, const uint32_t* perm, const u
   return hipGetLastError();
 }
 
+// ---- with_state reads of an Orswot (lib.rs:325-330) --------------------------------------------
+// A member's key stays in the member table after its last pair died, so "present" is "some pair of
+// the handle has cur != 0": one byte per member slot (the reserved slot of member ~0 included,
+// zeroed beforehand), set by one scan of the pair table with plain stores of 1.
+__global__ void __launch_bounds__(kBlock) k_ds_member_live(DsTables t, uint8_t* flags) {
+  const uint32_t cap = t.pmask + 1;
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < cap; i += gridDim.x * kBlock) {
+    const unsigned long long key = t.pkey[i];
+    if (key != kDsEmpty && t.cur[i] != 0) flags[key >> kDsActorBits] = 1;
+  }
+}
+
+// Orswot::contains(q[i]).val: member_find, then the handle's flag.  As k_gs_contains: kDsProbes
+// queries per lane and round, their keys, then their first primary slots, issued before any is
+// looked at; a first slot that holds the member settles the handle, anything else (another member,
+// an empty slot, the member ~0) goes through member_find: the primary window, then the overflow
+// table, the reserved slot.
+constexpr int kDsProbes = 4;
+
+__global__ void __launch_bounds__(kBlock) k_ds_contains(DsTables t, const uint8_t* flags, const unsigned long long* q,
+                                                        unsigned long long n, uint8_t* out) {
+  const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
+  for (unsigned long long base = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; base < n;
+       base += kDsProbes * stride) {
+    unsigned long long m[kDsProbes], g[kDsProbes], h[kDsProbes];
+#pragma unroll
+    for (int j = 0; j < kDsProbes; j++) {
+      const unsigned long long i = base + (unsigned long long)j * stride;
+      m[j] = i < n ? q[i] : kDsEmpty;
+    }
+#pragma unroll
+    for (int j = 0; j < kDsProbes; j++) g[j] = ld_volatile(t.mkey + ((uint32_t)mix64(m[j]) & t.smask));
+#pragma unroll
+    for (int j = 0; j < kDsProbes; j++) h[j] = member_handle(t, m[j], g[j], false);
+#pragma unroll
+    for (int j = 0; j < kDsProbes; j++) {
+      const unsigned long long i = base + (unsigned long long)j * stride;
+      if (i < n) out[i] = h[j] == kDsEmpty ? (uint8_t)0 : flags[h[j]];
+    }
+  }
+}
+
+// read().val.len(): the flags summed (out zeroed beforehand), one atomic per wave with members
+__global__ void __launch_bounds__(kBlock) k_ds_live_count(const uint8_t* flags, unsigned long long n, uint32_t* out) {
+  uint32_t c = 0;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; i < n;
+       i += (unsigned long long)gridDim.x * kBlock)
+    c += flags[i];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+}
+
+// read().val: the flagged handles' members into out, in no order (n_out zeroed beforehand; one
+// atomic per wave and round, as k_gs_collect)
+__global__ void __launch_bounds__(kBlock) k_ds_live_members(DsTables t, const uint8_t* flags, unsigned long long* out,
+                                                            uint32_t* n_out) {
+  const unsigned long long n = member_reserved(t) + 1;
+  const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
+  // (every lane of a wave runs the same number of rounds: the ballot sees whole waves)
+  for (unsigned long long i0 = (unsigned long long)blockIdx.x * kBlock; i0 < n; i0 += stride) {
+    const unsigned long long i = i0 + threadIdx.x;
+    const bool live = i < n && flags[i] != 0;
+    const unsigned long long b = __ballot(live);
+    if (b == 0) continue;
+    const int leader = __builtin_ctzll(b);
+    uint32_t base = 0;
+    if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(n_out, (uint32_t)__popcll(b));
+    base = (uint32_t)__shfl((int)base, leader);
+    if (live) out[base + (uint32_t)__popcll(b & ((1ull << (threadIdx.x & 63)) - 1))] = member_of(t, i);
+  }
+}
+
+// Orswot::contains(m).rm_clock for a set of members.  k_ds_mark_queries: qidx[handle of q[i]] =
+// i + 1 (qidx zeroed beforehand, one word per member slot; the queries are distinct).  Then one
+// scan of the pair table: a live pair of a marked handle leaves (query index, actor id) and its
+// counter at the next place of the output (n_out zeroed beforehand); places past cap are counted
+// and not written, and the host runs the scan again with room for the count.
+__global__ void __launch_bounds__(kBlock) k_ds_mark_queries(DsTables t, const unsigned long long* q, uint32_t n,
+                                                            uint32_t* qidx) {
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const unsigned long long h = member_find(t, q[i], false);
+    if (h != kDsEmpty) qidx[h] = i + 1;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_ds_member_clocks(DsTables t, const uint32_t* qidx, ulonglong2* out,
+                                                             uint32_t cap, uint32_t* n_out) {
+  const uint32_t slots = t.pmask + 1;
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < slots; i += gridDim.x * kBlock) {
+    const unsigned long long key = t.pkey[i];
+    if (key == kDsEmpty) continue;
+    const unsigned long long v = t.cur[i];
+    if (v == 0) continue;
+    const uint32_t qi = qidx[key >> kDsActorBits];
+    if (qi == 0) continue;
+    const uint32_t at = atomicAdd(n_out, 1u);
+    if (at < cap)
+      out[at] = make_ulonglong2(((unsigned long long)(qi - 1) << 32) | (uint32_t)(key & ((1u << kDsActorBits) - 1)), v);
+  }
+}
+
+hipError_t launch_ds_member_live(hipStream_t s, DsTables t, uint8_t* flags) {
+  hipLaunchKernelGGL(k_ds_member_live, dim3(blocks_for((uint64_t)t.pmask + 1, 2048)), dim3(kBlock), 0, s, t, flags);
+  return hipGetLastError();
+}
+
+hipError_t launch_ds_contains(hipStream_t s, DsTables t, const uint8_t* flags, const unsigned long long* q, uint64_t n,
+                              uint8_t* out, uint32_t grid_cap) {
+  if (n == 0) return hipSuccess;
+  const uint64_t per = kBlock * kDsProbes;  // queries a block takes per trip of its loop
+  hipLaunchKernelGGL(k_ds_contains, dim3(blocks_for((n + per - 1) / per * kBlock, grid_cap ? grid_cap : 2048)),
+                     dim3(kBlock), 0, s, t, flags, q, (unsigned long long)n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_ds_live_count(hipStream_t s, const uint8_t* flags, uint64_t n, uint32_t* out) {
+  hipLaunchKernelGGL(k_ds_live_count, dim3(blocks_for(n, 1024)), dim3(kBlock), 0, s, flags, (unsigned long long)n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_ds_live_members(hipStream_t s, DsTables t, const uint8_t* flags, unsigned long long* out,
+                                  uint32_t* n_out) {
+  hipLaunchKernelGGL(k_ds_live_members, dim3(blocks_for((uint64_t)t.smask + t.mmask + 3, 2048)), dim3(kBlock), 0, s, t,
+                     flags, out, n_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_ds_member_clocks(hipStream_t s, DsTables t, const unsigned long long* q, uint32_t n, uint32_t* qidx,
+                                   unsigned long long* out, uint32_t cap, uint32_t* n_out, bool mark) {
+  if (n == 0) return hipSuccess;
+  if (mark) hipLaunchKernelGGL(k_ds_mark_queries, dim3(blocks_for(n)), dim3(kBlock), 0, s, t, q, n, qidx);
+  hipLaunchKernelGGL(k_ds_member_clocks, dim3(blocks_for((uint64_t)t.pmask + 1, 2048)), dim3(kBlock), 0, s, t, qidx,
+                     reinterpret_cast<ulonglong2*>(out), cap, n_out);
+  return hipGetLastError();
+}
+
 hipError_t launch_mv_prep(hipStream_t s, const MvArgs& a) {
   if (a.n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_mv_prep, dim3(blocks_for(a.n)), dim3(kBlock), 0, s, a);

@@ -100,6 +100,12 @@ struct DsState {
   HostBuf rd_host, rd_small, rd_clock, rd_args_h, h_clock, rd_tailh;
   uint64_t uuid_ids = ~0ull;  // id count uuid_of_id / rank_of_id (and id_rank / rank_id) were built for
   std::vector<uint32_t> id_rank, rank_id;  // UUID-order rank of each stable id, and its inverse
+  // with_state reads (the end of this file).  state_gen: bumped by every path that changes the
+  // member or pair table (fold, state merge, column merge, local apply, reset, rebuild / growth);
+  // read_flags / read_len: the per-handle live flags and their sum as of read_gen
+  uint64_t state_gen = 1, read_gen = 0, read_len = 0;
+  DevBuf read_flags, read_q, read_ans, read_qidx, read_ent, read_cnt, read_col, read_sorted;
+  HostBuf read_host;
 };
 
 void ds_free(DsState* d) { delete d; }
@@ -137,6 +143,7 @@ DsTables tables(DsState* d) {
 
 int tables_alloc(ce_core* c, uint32_t cap, const FillRange* extra = nullptr) {
   DsState* d = c->ds;
+  d->state_gen++;  // (reset, rebuild, growth: every handle moves)
   ce_ctx* ctx = c->ctx;
   hipError_t e;
   const uint64_t mslots = (uint64_t)d->mcap_s + cap + 1;
@@ -272,6 +279,7 @@ int ensure_pairs(ce_core* c, uint64_t extra) {
     return c->ctx->hip_fail(e, "rebuild");
   d->used_pairs = n_live;
   d->live_pairs = n_live;
+  c->path_counts["ds_table_rebuilds"]++;
   return CE_OK;
 }
 
@@ -578,6 +586,7 @@ int flags_for(ce_core* c, const uint32_t* cbeg, const uint32_t* act, const unsig
 
 int finalize(ce_core* c) {
   DsState* d = c->ds;
+  d->state_gen++;
   uint32_t h[4];
   hipError_t e;
   if ((e = hipMemsetAsync(d->live.p, 0, 8, c->ctx->stream))) return c->ctx->hip_fail(e, "finalize");
@@ -605,6 +614,7 @@ int finalize(ce_core* c) {
 // passes false, and the sorted path is always correct)
 int orswot_fold(ce_core* c, const Counts& k, uint64_t kill_bound, bool adds_contig) {
   DsState* d = c->ds;
+  d->state_gen++;
   ce_ctx* ctx = c->ctx;
   hipStream_t s = ctx->stream;
   DsOps o = ops_view(d);
@@ -1649,6 +1659,7 @@ int orswot_merge_cols(ce_core* c, const IdDots& oclock,
                       const OtherCols& ocols, uint32_t n, uint32_t* live_async, bool* queued,
                       bool want_live) {
   DsState* d = c->ds;
+  d->state_gen++;
   ce_ctx* ctx = c->ctx;
   hipStream_t s = ctx->stream;
   int rc;
@@ -1868,6 +1879,7 @@ int ds_merge_states_device(ce_core* c, const uint8_t* out, const std::vector<uin
   // was a 51 us blit to host memory for ~20 KiB heads)
   const uint64_t kPrefix = d->head_hint;
   if (int rs = ds_settle(c)) return rs;
+  d->state_gen++;  // (the k-way merge below, and every path it falls back to)
   std::vector<DevState> ds(n);
   std::vector<std::vector<uint8_t>> host_pt(n);
   hipError_t e;
@@ -2873,6 +2885,7 @@ int ds_export_columns_device(ce_core* c, uint8_t* dst, uint64_t cap, uint64_t* l
 int ds_merge_columns_device(ce_core* c, const uint8_t* const* parts, const uint64_t* lens, uint32_t k) {
   if (int rs = ds_settle(c)) return rs;
   DsState* d = c->ds;
+  d->state_gen++;
   ce_ctx* ctx = c->ctx;
   hipStream_t s = ctx->stream;
   if (c->kind != CE_STATE_ORSWOT)
@@ -3356,6 +3369,196 @@ int ds_serialize(ce_core* c, std::vector<uint8_t>* out) {
     for (uint64_t m : *x.second) w.uint(m);
   }
   out->swap(w.b);
+  return CE_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// with_state reads (lib.rs:325-330): every one settles the queued fold / merge first and answers
+// for the tables as they then stand
+// ---------------------------------------------------------------------------------------
+namespace {
+
+// the per-handle live flags and their sum, rebuilt when a path that changes the tables ran since
+int ensure_live_flags(ce_core* c) {
+  DsState* d = c->ds;
+  if (d->read_gen == d->state_gen) return CE_OK;
+  ce_ctx* ctx = c->ctx;
+  hipStream_t s = ctx->stream;
+  const uint64_t slots = (uint64_t)d->mcap_s + d->pcap + 1;
+  hipError_t e;
+  uint32_t len = 0;
+  if ((e = d->read_flags.reserve(slots + 64)) || (e = d->read_cnt.reserve(64)) ||
+      (e = hipMemsetAsync(d->read_flags.p, 0, slots, s)) || (e = hipMemsetAsync(d->read_cnt.p, 0, 4, s)))
+    return ctx->hip_fail(e, "live flags");
+  const int t = ctx->tbegin("ds_member_live");
+  if ((e = launch_ds_member_live(s, tables(d), d->read_flags.as<uint8_t>()))) return ctx->hip_fail(e, "live flags");
+  ctx->tend(t);
+  if ((e = launch_ds_live_count(s, d->read_flags.as<uint8_t>(), slots, d->read_cnt.as<uint32_t>())) ||
+      (e = hipMemcpyAsync(&len, d->read_cnt.p, 4, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+    return ctx->hip_fail(e, "live flags");
+  d->read_len = len;
+  d->read_gen = d->state_gen;
+  c->path_counts["ds_live_flag_builds"]++;
+  return CE_OK;
+}
+
+}  // namespace
+
+int ds_contains_device(ce_core* c, const uint64_t* d_members, uint64_t n, uint8_t* d_out) {
+  int rc;
+  if ((rc = ds_settle(c)) || n == 0 || (rc = ensure_live_flags(c))) return rc;
+  DsState* d = c->ds;
+  ce_ctx* ctx = c->ctx;
+  hipError_t e;
+  const int t = ctx->tbegin("ds_contains");
+  if ((e = launch_ds_contains(ctx->stream, tables(d), d->read_flags.as<uint8_t>(),
+                              reinterpret_cast<const unsigned long long*>(d_members), n, d_out, test_grid_cap())))
+    return ctx->hip_fail(e, "orswot contains");
+  ctx->tend(t);
+  if ((e = stream_wait(ctx->stream))) return ctx->hip_fail(e, "orswot contains");
+  return CE_OK;
+}
+
+int ds_set_len(ce_core* c, uint64_t* n) {
+  int rc;
+  if ((rc = ds_settle(c)) || (rc = ensure_live_flags(c))) return rc;
+  *n = c->ds->read_len;
+  return CE_OK;
+}
+
+// the flagged handles' members compacted, then the radix sort of the serializer
+int ds_members_device(ce_core* c, uint64_t* d_dst, uint64_t cap, uint64_t* n) {
+  int rc = ds_set_len(c, n);
+  if (rc || *n == 0 || cap < *n) return rc;
+  DsState* d = c->ds;
+  ce_ctx* ctx = c->ctx;
+  hipStream_t s = ctx->stream;
+  const uint32_t nl = (uint32_t)*n;
+  hipError_t e;
+  size_t tb = 0;
+  if ((e = d->read_col.reserve(nl * 8ull + 64)) || (e = d->read_sorted.reserve(nl * 8ull + 64)) ||
+      (e = d->read_ent.reserve(nl * 8ull + 64)) ||
+      (e = ds_sort_pairs_u64(nullptr, tb, nullptr, nullptr, nullptr, nullptr, nl, s)) ||
+      (e = d->cub_tmp.reserve(tb + 256)))
+    return ctx->hip_fail(e, "orswot members");
+  tb = d->cub_tmp.cap;
+  uint32_t* vin = d->read_ent.as<uint32_t>();  // (the sort carries a value column: not read here)
+  const int t = ctx->tbegin("ds_members");
+  if ((e = hipMemsetAsync(d->read_cnt.p, 0, 4, s)) ||
+      (e = launch_ds_live_members(s, tables(d), d->read_flags.as<uint8_t>(), d->read_col.as<unsigned long long>(),
+                                  d->read_cnt.as<uint32_t>())) ||
+      (e = ds_sort_pairs_u64(d->cub_tmp.p, tb, d->read_col.as<unsigned long long>(),
+                             d->read_sorted.as<unsigned long long>(), vin, vin + nl, nl, s)))
+    return ctx->hip_fail(e, "orswot members");
+  ctx->tend(t);
+  if ((e = hipMemcpyAsync(d_dst, d->read_sorted.p, nl * 8ull, hipMemcpyDeviceToDevice, s)) || (e = stream_wait(s)))
+    return ctx->hip_fail(e, "orswot members");
+  return CE_OK;
+}
+
+// Orswot: the clock; MVReg: the join of the values' clocks (MVReg::read().add_clock).  Counters
+// above zero only, in no order.
+int ds_read_clock(ce_core* c, Dots* out) {
+  if (int rs = ds_settle(c)) return rs;
+  DsState* d = c->ds;
+  out->clear();
+  if (c->kind == CE_STATE_MVREG) {
+    std::map<uint32_t, uint64_t> join;
+    for (auto& v : d->vals)
+      for (auto& x : v.first) join[x.first] = std::max(join[x.first], x.second);
+    for (auto& x : join)
+      if (x.second) out->push_back({c->id_actor[x.first], x.second});
+    return CE_OK;
+  }
+  const uint32_t na = std::min<uint32_t>((uint32_t)c->id_actor.size(), d->clock_cap);
+  hipError_t e;
+  if ((e = d->read_host.reserve(na * 8ull + 64))) return c->ctx->hip_fail(e, "clock download");
+  const unsigned long long* ck = d->read_host.as<unsigned long long>();
+  if (na && ((e = hipMemcpyAsync(d->read_host.p, d->clock.p, na * 8ull, hipMemcpyDeviceToHost, c->ctx->stream)) ||
+             (e = stream_wait(c->ctx->stream))))
+    return c->ctx->hip_fail(e, "clock download");
+  for (uint32_t i = 0; i < na; i++)
+    if (ck[i]) out->push_back({c->id_actor[i], ck[i]});
+  return CE_OK;
+}
+
+// Orswot::contains(m).rm_clock = entries[m] for n members: out = u32 beg[n + 1], padded to 8
+// bytes, then 24-byte entries (uuid16, u64 LE counter) ascending by UUID bytes within a member,
+// members in query order (an absent member: an empty range)
+int ds_member_clocks(ce_core* c, const uint64_t* members, uint32_t n, std::vector<uint8_t>* out) {
+  if (int rs = ds_settle(c)) return rs;
+  DsState* d = c->ds;
+  ce_ctx* ctx = c->ctx;
+  hipStream_t s = ctx->stream;
+  // the device marks handles: each member once, a repeated query shares its first one's entries
+  std::unordered_map<uint64_t, uint32_t> first;
+  std::vector<uint64_t> uniq;
+  std::vector<uint32_t> uidx(n);
+  for (uint32_t i = 0; i < n; i++) {
+    auto it = first.find(members[i]);
+    if (it == first.end()) {
+      it = first.emplace(members[i], (uint32_t)uniq.size()).first;
+      uniq.push_back(members[i]);
+    }
+    uidx[i] = it->second;
+  }
+  const uint32_t nu = (uint32_t)uniq.size();
+  std::vector<std::vector<std::pair<Uuid, uint64_t>>> per(nu);
+  if (nu) {
+    const uint64_t slots = (uint64_t)d->mcap_s + d->pcap + 1;
+    hipError_t e;
+    if ((e = d->read_q.reserve(nu * 8ull + 64)) || (e = d->read_qidx.reserve(slots * 4 + 64)) ||
+        (e = d->read_cnt.reserve(64)) ||
+        (e = hipMemcpyAsync(d->read_q.p, uniq.data(), nu * 8ull, hipMemcpyHostToDevice, s)) ||
+        (e = hipMemsetAsync(d->read_qidx.p, 0, slots * 4, s)))
+      return ctx->hip_fail(e, "member clocks");
+    uint32_t cap = std::max<uint32_t>(4096, 64 * nu), found = 0;
+    for (int round = 0;; round++) {
+      if ((e = d->read_ent.reserve(cap * 16ull + 64)) || (e = hipMemsetAsync(d->read_cnt.p, 0, 4, s)))
+        return ctx->hip_fail(e, "member clocks");
+      const int t = ctx->tbegin("ds_member_clocks");
+      if ((e = launch_ds_member_clocks(s, tables(d), d->read_q.as<unsigned long long>(), nu,
+                                       d->read_qidx.as<uint32_t>(), d->read_ent.as<unsigned long long>(), cap,
+                                       d->read_cnt.as<uint32_t>(), round == 0)))
+        return ctx->hip_fail(e, "member clocks");
+      ctx->tend(t);
+      if ((e = hipMemcpyAsync(&found, d->read_cnt.p, 4, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+        return ctx->hip_fail(e, "member clocks");
+      if (found <= cap) break;
+      if (round) return ctx->fail(CE_ERR_DEVICE, "member clocks did not fit their count");
+      cap = found;  // (more dots than the first guess: once more with room for every one)
+    }
+    std::vector<unsigned long long> ent(2ull * found);
+    if (found && ((e = hipMemcpyAsync(ent.data(), d->read_ent.p, found * 16ull, hipMemcpyDeviceToHost, s)) ||
+                  (e = stream_wait(s))))
+      return ctx->hip_fail(e, "member clocks");
+    for (uint32_t k = 0; k < found; k++) {
+      const uint32_t qi = (uint32_t)(ent[2 * k] >> 32), aid = (uint32_t)ent[2 * k];
+      if (qi >= nu || aid >= c->id_actor.size()) return ctx->fail(CE_ERR_DEVICE, "member clocks: entry out of range");
+      per[qi].push_back({c->id_actor[aid], ent[2 * k + 1]});
+    }
+    for (auto& v : per) std::sort(v.begin(), v.end());
+  }
+  std::vector<uint32_t> beg(n + 1, 0);
+  for (uint32_t i = 0; i < n; i++) beg[i + 1] = beg[i] + (uint32_t)per[uidx[i]].size();
+  const size_t head = ((n + 1) * 4ull + 7) & ~7ull;
+  out->assign(head + 24ull * beg[n], 0);
+  std::memcpy(out->data(), beg.data(), (n + 1) * 4ull);
+  uint8_t* p = out->data() + head;
+  for (uint32_t i = 0; i < n; i++)
+    for (auto& x : per[uidx[i]]) {
+      std::memcpy(p, x.first.data(), 16);
+      std::memcpy(p + 16, &x.second, 8);
+      p += 24;
+    }
+  return CE_OK;
+}
+
+// MVReg::read().val in the order ds_serialize writes `vals`
+int ds_mvreg_read(ce_core* c, std::vector<uint64_t>* out) {
+  if (int rs = ds_settle(c)) return rs;
+  out->clear();
+  for (auto& v : c->ds->vals) out->push_back(v.second);
   return CE_OK;
 }
 

@@ -87,6 +87,10 @@ hipError_t launch_gs_state_insert(hipStream_t s, GsTable t, const uint8_t* base,
                                   uint32_t total, const uint32_t* runs);
 // every member of src into dst (the batch's commit, and a growth's rehash)
 hipError_t launch_gs_move(hipStream_t s, GsTable src, GsTable dst);
+// GSet::contains(q[i]) against t for i < n: out[i] = 1 or 0 (k_gs_contains: a grid-stride loop,
+// several probes in flight per lane).  grid_cap: the most blocks to launch (0: 2048)
+hipError_t launch_gs_contains(hipStream_t s, GsTable t, const unsigned long long* q, uint64_t n, uint8_t* out,
+                              uint32_t grid_cap);
 // the live members of t, in no order, into out[0..*n_out) (*n_out zero before the launch)
 hipError_t launch_gs_collect(hipStream_t s, GsTable t, unsigned long long* out, uint32_t* n_out);
 // the serializer over the sorted members v[0..n): w[i] = element i's encoded length (1, 2, 3, 5

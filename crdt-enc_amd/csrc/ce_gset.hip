@@ -319,6 +319,42 @@ __global__ __launch_bounds__(256) void k_gs_collect(GsTable t, unsigned long lon
   }
 }
 
+// GSet::contains for a column of queries against the committed table: out[i] = 1 or 0.  A probe is
+// one random 8-byte read of a table far larger than L2, and a lane that waits for one before it
+// issues the next pays the whole miss each time: a lane takes kGsProbes queries per round, their
+// keys, then their first slots, issued together before any is looked at.  Only the first slot can
+// be issued ahead; a collision walks on in gs_contains.  The member 0 is held out of band.
+constexpr int kGsProbes = 8;
+
+__global__ __launch_bounds__(256) void k_gs_contains(GsTable t, const unsigned long long* q, unsigned long long n,
+                                                     uint8_t* out) {
+  const uint8_t zero = ld_word(&t.meta[kGsZero]) ? 1 : 0;
+  const unsigned long long stride = (unsigned long long)gridDim.x * 256;
+  for (unsigned long long base = (unsigned long long)blockIdx.x * 256 + threadIdx.x; base < n;
+       base += kGsProbes * stride) {
+    unsigned long long v[kGsProbes], s[kGsProbes];
+#pragma unroll
+    for (int j = 0; j < kGsProbes; j++) {
+      const unsigned long long i = base + (unsigned long long)j * stride;
+      v[j] = i < n ? q[i] : 0ull;
+    }
+    // (a lane past the end probes the slot of key 0: inside the table, never looked at)
+#pragma unroll
+    for (int j = 0; j < kGsProbes; j++) s[j] = ld_slot(&t.slots[gs_hash(v[j]) & t.mask]);
+#pragma unroll
+    for (int j = 0; j < kGsProbes; j++) {
+      const unsigned long long i = base + (unsigned long long)j * stride;
+      if (i >= n) continue;
+      uint8_t r;
+      if (v[j] == 0) r = zero;
+      else if (s[j] == v[j]) r = 1;
+      else if (s[j] == 0) r = 0;
+      else r = gs_contains(t, v[j]) ? 1 : 0;  // (a collision: the rest of the run)
+      out[i] = r;
+    }
+  }
+}
+
 // the serializer: an element's encoded length (its smallest unsigned form), and the writer
 __device__ __forceinline__ uint32_t gs_width(unsigned long long v) {
   return v <= 0x7f ? 1u : v <= 0xff ? 2u : v <= 0xffff ? 3u : v <= 0xffffffffull ? 5u : 9u;
@@ -410,6 +446,17 @@ hipError_t launch_gs_write(hipStream_t s, const unsigned long long* v, const uin
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_gs_write, dim3(blocks_for(n)), dim3(256), 0, s, v, off, n, out, clear_len_at,
                      (unsigned long long)head_len);
+  return hipGetLastError();
+}
+
+hipError_t launch_gs_contains(hipStream_t s, GsTable t, const unsigned long long* q, uint64_t n, uint8_t* out,
+                              uint32_t grid_cap) {
+  if (n == 0) return hipSuccess;
+  const uint64_t per = 256 * kGsProbes;  // queries a block takes per trip of its loop
+  uint64_t blocks = (n + per - 1) / per;
+  const uint32_t cap = grid_cap ? grid_cap : 2048;
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(k_gs_contains, dim3((uint32_t)blocks), dim3(256), 0, s, t, q, (unsigned long long)n, out);
   return hipGetLastError();
 }
 

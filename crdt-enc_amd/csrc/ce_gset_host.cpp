@@ -499,6 +499,45 @@ int gs_members_sorted(ce_core* c, std::vector<uint64_t>* out) {
   return CE_OK;
 }
 
+// ---- with_state reads (lib.rs:325-330): the committed table only; a batch left pending by the
+// sharded ingest lives in the batch table and is no part of any answer ----
+
+// GSet::contains over a query column in HBM; complete on return
+int gs_contains_device(ce_core* c, const uint64_t* d_members, uint64_t n, uint8_t* d_out) {
+  if (n == 0) return CE_OK;
+  ce_ctx* ctx = c->ctx;
+  hipError_t e;
+  const int t = ctx->tbegin("gs_contains");
+  if ((e = launch_gs_contains(ctx->stream, committed(c->gs), reinterpret_cast<const unsigned long long*>(d_members), n,
+                              d_out, test_grid_cap())))
+    return ctx->hip_fail(e, "gset contains");
+  ctx->tend(t);
+  if ((e = stream_wait(ctx->stream))) return ctx->hip_fail(e, "gset contains");
+  return CE_OK;
+}
+
+// read().val.len(): the claimed slots and the out-of-band member 0
+int gs_set_len(ce_core* c, uint64_t* n) {
+  uint32_t hm[kMetaWords];
+  int rc = read_meta(c, hm);
+  if (rc) return rc;
+  *n = (uint64_t)hm[kGsCount] + (hm[kGsZero] ? 1u : 0u);
+  return CE_OK;
+}
+
+// read().val ascending into d_dst: the serializer's collect and sort, then one device copy
+int gs_members_device(ce_core* c, uint64_t* d_dst, uint64_t cap, uint64_t* n) {
+  int rc = gs_set_len(c, n);
+  if (rc || *n == 0 || cap < *n) return rc;
+  uint32_t got = 0;
+  if ((rc = collect_sorted(c, &got))) return rc;
+  hipError_t e;
+  if ((e = hipMemcpyAsync(d_dst, c->gs->sorted.p, (size_t)got * 8, hipMemcpyDeviceToDevice, c->ctx->stream)) ||
+      (e = stream_wait(c->ctx->stream)))
+    return c->ctx->hip_fail(e, "gset members");
+  return CE_OK;
+}
+
 namespace {
 
 // The device writer.  head: the clear text up to and including a5"state" (the host's part: the

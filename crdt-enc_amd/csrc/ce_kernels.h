@@ -249,6 +249,13 @@ hipError_t launch_gate(hipStream_t s, const GateArgs& g);
 // dst[i] = max(dst[i], src[i])
 hipError_t launch_merge_max(hipStream_t s, unsigned long long* dst,
                             const unsigned long long* src, uint32_t n);
+// the with_state reads of the dense kinds: each of n_planes planes (cap words apiece) summed to
+// 128 bits at out[2 p] (low) / out[2 p + 1] (high), out zeroed beforehand; and dst[i] =
+// src[idx[i]] for m indices (0 where idx[i] is ~0)
+hipError_t launch_sum_u64_128(hipStream_t s, const unsigned long long* planes, uint32_t cap, uint32_t n_planes,
+                              unsigned long long* out);
+hipError_t launch_gather_u64(hipStream_t s, const unsigned long long* src, const uint32_t* idx, uint32_t m,
+                             unsigned long long* dst);
 // launch_merge_max unless the counter block flags a batch that cannot commit as folded
 hipError_t launch_merge_max_if(hipStream_t s, unsigned long long* dst, const unsigned long long* src,
                                uint32_t n, const uint32_t* counters);

@@ -1721,4 +1721,75 @@ hipError_t launch_serialize_vclock(hipStream_t s, const unsigned long long* nov,
   return hipGetLastError();
 }
 
+// ---- with_state reads of the dense kinds (lib.rs:325-330) --------------------------------------
+// GCounter::read / PNCounter::read: plane blockIdx.y of `planes` (cap words each) summed to 128
+// bits at out[2 y] (low) and out[2 y + 1] (high), both zeroed beforehand.  A lane carries from its
+// low word into its high word; lanes, then waves, are combined the same way; a block adds its sum
+// with two 64-bit atomics, the low word's returning add telling whether it wrapped.
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int o) {
+  return ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o) << 32) |
+         (uint32_t)__shfl_xor((int)(uint32_t)v, o);
+}
+
+__global__ __launch_bounds__(256) void k_sum_u64_128(const unsigned long long* __restrict__ planes, uint32_t cap,
+                                                     unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long s_lo[4], s_hi[4];
+  const unsigned long long* src = planes + (size_t)blockIdx.y * cap;
+  unsigned long long lo = 0, hi = 0;
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < cap; i += gridDim.x * 256) {
+    const unsigned long long v = src[i];
+    lo += v;
+    hi += lo < v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long l2 = shfl_xor_u64(lo, o), h2 = shfl_xor_u64(hi, o);
+    lo += l2;
+    hi += h2 + (lo < l2);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_lo[threadIdx.x >> 6] = lo;
+    s_hi[threadIdx.x >> 6] = hi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    lo = s_lo[0];
+    hi = s_hi[0];
+    for (int w = 1; w < 4; w++) {
+      lo += s_lo[w];
+      hi += s_hi[w] + (lo < s_lo[w]);
+    }
+    if (lo | hi) {
+      const unsigned long long old = atomicAdd(&out[2 * blockIdx.y], lo);
+      hi += (old + lo) < old ? 1u : 0u;
+      if (hi) atomicAdd(&out[2 * blockIdx.y + 1], hi);
+    }
+  }
+}
+
+hipError_t launch_sum_u64_128(hipStream_t s, const unsigned long long* planes, uint32_t cap, uint32_t n_planes,
+                              unsigned long long* out) {
+  if (cap == 0 || n_planes == 0) return hipSuccess;
+  const uint32_t blocks = min((cap + 255) / 256, 256u);
+  hipLaunchKernelGGL(k_sum_u64_128, dim3(blocks, n_planes), dim3(256), 0, s, planes, cap, out);
+  return hipGetLastError();
+}
+
+// VClock::get for m actors at once: dst[i] = idx[i] == ~0 ? 0 : src[idx[i]] (dst may be mapped
+// pinned memory)
+__global__ void k_gather_u64(const unsigned long long* __restrict__ src, const uint32_t* __restrict__ idx, uint32_t m,
+                             unsigned long long* __restrict__ dst) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
+    const uint32_t k = idx[i];
+    dst[i] = k == 0xffffffffu ? 0ull : src[k];
+  }
+}
+
+hipError_t launch_gather_u64(hipStream_t s, const unsigned long long* src, const uint32_t* idx, uint32_t m,
+                             unsigned long long* dst) {
+  if (m == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gather_u64, dim3(min((m + 255) / 256, 1024u)), dim3(256), 0, s, src, idx, m, dst);
+  return hipGetLastError();
+}
+
 }  // namespace ce

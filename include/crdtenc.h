@@ -522,6 +522,48 @@ int ce_shard_window_host(uint32_t m, const uint64_t *e0, const int64_t *stats, u
 int ce_shard_window_exact(uint32_t m, const uint64_t *e0, const uint32_t *fa, const uint64_t *fv,
                           uint64_t n, uint64_t *hi);
 
+/* ---------------------------------------------------------------------------------------- */
+/* Core::with_state (crdt-enc/src/lib.rs:325-330) answered on the device: the reads a client   */
+/* makes of the merged state, without serializing it (ce_core_state_bytes) and parsing it back. */
+/* Every call takes the context lock, selects the core's device and answers for the COMMITTED   */
+/* state: a fold or merge queued without a host wait is settled first (as ce_core_settle); a    */
+/* GSet batch left pending by ce_core_gset_ingest_ops_device_sharded is no part of the answer   */
+/* until ce_core_gset_pending_commit; a poisoned dot-set core returns its error.  A state kind  */
+/* the call does not serve: CE_ERR_INVALID_ARG, and no output is touched.  n = 0 (m = 0)        */
+/* succeeds, with NULL arrays allowed.                                                          */
+/* ---------------------------------------------------------------------------------------- */
+/* lib.rs:325-330 with Orswot<u64>::contains(m).val / GSet<u64>::contains(m), batched over a u64
+ * column in device memory: d_out[i] = 1 or 0.  Orswot and GSet.  Complete on return. */
+int ce_core_set_contains_device(ce_core *c, const uint64_t *d_members, uint64_t n, uint8_t *d_out);
+/* The same over host buffers (uploaded, answered on the device, downloaded). */
+int ce_core_set_contains(ce_core *c, const uint64_t *members, uint64_t n, uint8_t *out);
+/* lib.rs:325-330 with Orswot::read().val.len() / GSet::read().len().  Orswot and GSet. */
+int ce_core_set_len(ce_core *c, uint64_t *n);
+/* lib.rs:325-330 with Orswot::read().val / GSet::read() as an ascending u64 column in device
+ * memory (BTreeSet order).  *n is always the member count; nothing is written when cap < *n (CE_OK:
+ * grow and call again).  Orswot and GSet.  Complete on return. */
+int ce_core_set_members_device(ce_core *c, uint64_t *d_dst, uint64_t cap, uint64_t *n);
+/* lib.rs:325-330 with GCounter::read() / PNCounter::read() (a BigInt: p - n): the magnitude as
+ * 128 bits (mag[0] the low word) and the sign apart (*negative = 1 only when p < n).  GCounter and
+ * PNCounter (a VClock has no read()). */
+int ce_core_counter_read(ce_core *c, uint64_t mag[2], int *negative);
+/* lib.rs:325-330 with VClock::get(actor) for m actors (16 bytes each), 0 for an unknown actor.
+ * which: 0 = a VClock's dots / a GCounter's inner / a PNCounter's p / an Orswot's clock / an
+ * MVReg's read clock (the join of its values' clocks, MVReg::read().add_clock); 1 = a PNCounter's n
+ * (CE_ERR_INVALID_ARG for any other kind).  Every kind but GSet. */
+int ce_core_clock_get(ce_core *c, int which, const uint8_t *actors, uint32_t m, uint64_t *out);
+/* The same clock whole (VClock::dots, lib.rs:325-330): 24-byte entries (actor UUID, u64 LE
+ * counter), counters above zero only, ascending by UUID bytes (BTreeMap order).  ce_buf_free. */
+int ce_core_read_clock(ce_core *c, int which, ce_buf *out);
+/* lib.rs:325-330 with Orswot::contains(m).rm_clock (= entries[m], the context an Rm of m carries)
+ * for n members: u32 beg[n + 1] (host byte order), padded with zeros to a multiple of 8 bytes, then
+ * 24-byte entries as above; member i's are entries [beg[i], beg[i + 1]), members in query order,
+ * an absent member an empty range.  Orswot only.  ce_buf_free. */
+int ce_core_orswot_member_clocks(ce_core *c, const uint64_t *members, uint32_t n, ce_buf *out);
+/* lib.rs:325-330 with MVReg::read().val: k u64 LE values, in the order ce_core_state_bytes writes
+ * `vals`.  MVReg only.  ce_buf_free. */
+int ce_core_mvreg_read(ce_core *c, ce_buf *out);
+
 /* Diagnostics: how many times a code path ran on this core ("states_device_read",
  * "states_host_parse", "compact_device_writer"; per multi-segment op file "segdec_records"
  * (folded from the segment pass's records) and "segdec_fallback" (decoded whole)); lets tests
