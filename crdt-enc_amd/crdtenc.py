@@ -54,7 +54,7 @@ EXPORTS = [
     "ce_keys_decode", "ce_keys_from_remote_metas", "ce_keys_merge", "ce_keys_free",
     "ce_keys_count", "ce_keys_latest", "ce_keys_get", "ce_keys_at", "ce_core_set_keys",
     "ce_core_apply_ops_batch", "ce_core_ingest_ops_iov", "ce_core_ingest_states_iov", "ce_core_compact_ops_iov",
-    "ce_core_path_count", "ce_ctx_clock_probe",
+    "ce_core_path_count", "ce_ctx_clock_probe", "ce_ctx_wave_stamps",
     "ce_shard_owner", "ce_shard_owners", "ce_shard_stats_len", "ce_core_shard_stats",
     "ce_core_shard_window", "ce_core_ingest_ops_device_sharded", "ce_core_pending_export",
     "ce_core_pending_commit", "ce_core_writer_versions", "ce_shard_stats_host",
@@ -417,6 +417,20 @@ class Context:
         self.check(lib().ce_ctx_clock_probe(self.p, ctypes.c_void_p(stream_ptr), ctypes.c_void_p(out_ptr),
                                             ctypes.c_uint32(blocks), ctypes.c_uint32(samples),
                                             ctypes.c_uint32(ticks)), "clock_probe")
+
+    def wave_stamps(self):
+        """Diagnostics: the stamps of the last fused open launched with CE_TEST_WAVE_STAMPS=1 in the
+        environment (ce_ctx_wave_stamps) -> uint64 array [waves, 4]: entered, left (100 MHz ticks),
+        HW_ID | XCC_ID << 32, the build's schedule (groups per chunk | fixed percent << 32).  [0, 4]
+        when the context's last fused open was not stamped."""
+        import numpy as np
+        n = ctypes.c_uint32(0)
+        self.check(lib().ce_ctx_wave_stamps(self.p, None, ctypes.c_uint32(0), ctypes.byref(n)), "wave_stamps")
+        out = np.zeros((n.value, 4), dtype=np.uint64)
+        if n.value:
+            self.check(lib().ce_ctx_wave_stamps(self.p, ctypes.c_void_p(out.ctypes.data), ctypes.c_uint32(n.value),
+                                                ctypes.byref(n)), "wave_stamps")
+        return out[:n.value]
 
     # ---- Cryptor ----
     def gen_key(self):

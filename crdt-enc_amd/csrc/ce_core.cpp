@@ -928,9 +928,15 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
 
   // 2) GPU: single-page files: open + decode + fold fused; larger files: segments + decode
   ctx->open_log.grid_cap = test_grid_cap();
+  ctx->open_log.stamps = test_wave_stamps(ctx);
+  ctx->open_log.stamp_waves = 0;  // this ingest's launches, if stamped, are the ones to read
   auto run_fold = [&](const uint8_t* only) -> int {
     da.only = only;
     da.large_only = 1;
+    // a fold over the same counter block (host gate, misses): the fused kernel's ticket was drawn
+    // past the batch by the launch before, so it starts from zero again, as [4] does
+    if (only && (e = hipMemsetAsync(ctx->counters.as<uint32_t>() + kTicketWord, 0, 4, ctx->stream)))
+      return ctx->hip_fail(e, "ticket");
     if (pnc) {  // always the default geometry's PNCounter form (no env-selected alternates)
       hipEvent_t t0, t1;
       (void)ctx->tlaunch("open_fold_small", &t0, &t1);

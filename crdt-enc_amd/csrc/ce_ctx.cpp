@@ -68,6 +68,17 @@ uint32_t test_grid_cap() {
   return v < 1 ? 0u : (uint32_t)std::min<long>(v, 1l << 30);
 }
 
+unsigned long long* test_wave_stamps(ce_ctx* ctx) {
+  const char* e = getenv("CE_TEST_WAVE_STAMPS");
+  if (!e || atoi(e) < 1) return nullptr;
+  const size_t bytes = (size_t)kStampWaves * kStampWords * 8;
+  if (ctx->stamps.reserve(bytes) != hipSuccess || hipMemsetAsync(ctx->stamps.p, 0, bytes, ctx->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return ctx->stamps.as<unsigned long long>();
+}
+
 uint32_t grid_waves_for(uint32_t work) {
   // 256 CUs x 32 resident waves (segment kernel: <= 64 VGPRs -> 8 waves / SIMD)
   uint32_t full = 256u * 32u;
@@ -166,6 +177,8 @@ int device_open(ce_ctx* ctx, const uint8_t* d_blob, const uint64_t* d_offs, uint
   ctx->tend(t);
   if (small_lanes) {
     ctx->open_log.grid_cap = test_grid_cap();
+    ctx->open_log.stamps = nullptr;  // no kernel of this path is stamped: none to read afterwards
+    ctx->open_log.stamp_waves = 0;
     DecodeArgs da{};
     da.pt = d_out;
     da.blob = d_blob;
@@ -422,6 +435,23 @@ int ce_ctx_clock_probe(ce_ctx* c, void* hip_stream, uint64_t* d_out, uint32_t bl
                                           reinterpret_cast<unsigned long long*>(d_out), blocks,
                                           samples, ticks);
   return e == hipSuccess ? CE_OK : c->hip_fail(e, "clock probe");
+}
+
+int ce_ctx_wave_stamps(ce_ctx* c, uint64_t* out, uint32_t cap_waves, uint32_t* n_waves) {
+  if (!c || !n_waves || (cap_waves && !out)) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  (void)hipSetDevice(c->device);
+  const uint32_t n = c->stamps.p ? c->open_log.stamp_waves : 0;
+  *n_waves = n;
+  const uint32_t k = std::min(n, cap_waves);
+  if (k == 0) return CE_OK;
+  hipError_t e;
+  if ((e = hipMemcpyAsync(out, c->stamps.p, (size_t)k * kStampWords * 8, hipMemcpyDeviceToHost, c->stream)) ||
+      (e = hipStreamSynchronize(c->stream)))
+    return c->hip_fail(e, "wave stamps");
+  // the schedule this library was built with, for a caller that places its cases by it
+  for (uint32_t i = 0; i < k; i++) out[(size_t)kStampWords * i + 3] = (uint64_t)CE_DYN_CHUNK | ((uint64_t)CE_DYN_STATIC_PCT << 32);
+  return CE_OK;
 }
 
 int ce_ctx_timing_read(ce_ctx* c, const char* kernel, double* total_ms, uint64_t* launches) {

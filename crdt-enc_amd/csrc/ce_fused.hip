@@ -1659,12 +1659,46 @@ void k_open_fold_v3(DecodeArgs a) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t grp = lane / LPF, sub = lane % LPF;
   uint8_t* fl = lds + grp * kRegionStride2;
-  // a wave takes a contiguous run of file groups (load_ops order: a writer's files are adjacent,
-  // so the lane's actor cache and pending max carry over from file to file)
+  // A wave takes runs of consecutive file groups (load_ops order: a writer's files are adjacent,
+  // so the lane's actor cache and pending max carry over from file to file): first its fixed run
+  // of `fixed` groups, CE_DYN_STATIC_PCT percent of an even share and drawn with no atomic, then
+  // chunks of CE_DYN_CHUNK groups drawn from the ticket word until the batch runs out, so that a
+  // wave that gets ahead takes more and every wave stays resident to the end.  Chunk t is groups
+  // [dyn0 + t CE_DYN_CHUNK, + CE_DYN_CHUNK).  Lane 0 draws one chunk ahead (`tk`, its lane 0): the
+  // iteration that takes a run's last group reads the ticket of the run after it (the next
+  // parameters are loaded from there) and issues the atomic for the one after that, ahead of its
+  // own loads.  The ticket that is read was drawn CE_DYN_CHUNK iterations before and landed long
+  // ago, so reading it waits for nothing; the atomic just issued shares its latency with that
+  // iteration's own parameter and ciphertext loads (vmcnt counts in order: their first wait is
+  // also a wait for it), once per chunk.  What the loop carries from group to
+  // group (the speculated Dot length, the actor cache, the pending (slot, max), AuthFails) are
+  // caches and max-folds, right for any order of the groups.
   const uint32_t ngroups = (a.n + F - 1) / F;
-  const uint32_t g_end = (uint32_t)(((uint64_t)(blockIdx.x + 1) * ngroups) / gridDim.x);
-  uint32_t g = bcast((uint32_t)(((uint64_t)blockIdx.x * ngroups) / gridDim.x));
-  FilePre2 nx = load_pre2(a, g * F + grp);
+  const uint32_t fixed = (uint32_t)((uint64_t)(ngroups / gridDim.x) * CE_DYN_STATIC_PCT / 100u);
+  const uint32_t dyn0 = fixed * gridDim.x;
+  uint32_t tk = 0;
+  auto draw = [&] {
+    // The word's index through an opaque VGPR: the compiler then takes the address for a per-lane
+    // one and leaves the atomic as written.  With a uniform address it rewrites a uniform
+    // atomicAdd into a ballot count, one lane's atomic and a broadcast, which waits for the
+    // atomic's return on the spot -- the latency this draw-ahead exists to hide.
+    uint32_t tw = kTicketWord;
+    asm volatile("" : "+v"(tw));
+    if (lane == 0) tk = atomicAdd(a.counters + tw, 1u);
+  };
+  auto chunk = [&](uint32_t& lo, uint32_t& hi) {  // the drawn chunk, empty at ngroups when past the end
+    const uint64_t s = dyn0 + (uint64_t)bcast(tk) * CE_DYN_CHUNK;
+    lo = s < ngroups ? (uint32_t)s : ngroups;
+    hi = ngroups - lo < CE_DYN_CHUNK ? ngroups : lo + CE_DYN_CHUNK;
+    draw();
+  };
+  draw();
+  // gn: the group the parameters in nx belong to, the next one the loop takes; c_end: its run's end
+  uint32_t gn = bcast(blockIdx.x * fixed), c_end = gn + fixed;
+  if (fixed == 0) chunk(gn, c_end);
+  // (tests and tools: when the wave entered the loop, stored at once so the loop carries nothing)
+  if (a.stamps && lane == 0) a.stamps[(uint64_t)kStampWords * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+  FilePre2 nx = load_pre2(a, gn * F + grp);
   const SupVers sup(a);
   DecState S{PN ? 51u : 38u, 0, 0, 0, 0, 0xffffffffu};
   GsCounts gsc;
@@ -1689,10 +1723,12 @@ void k_open_fold_v3(DecodeArgs a) {
   wsrc(qy, (uint32_t)offsetof(PolyAux, r48), qy + 3u, y_base, y_stride);
 
   uint4 ct[BPL][4];
-  for (; g < g_end; g++) {
-    const uint32_t f = g * F + grp;
+  while (gn < ngroups) {
+    const uint32_t f = gn * F + grp;
     const FilePre2 cur = nx;
-    if (EARLY) nx = load_pre2(a, (g + 1) * F + grp);
+    // the group after this one: the next of the run, or the first of the chunk drawn before
+    if (++gn == c_end) chunk(gn, c_end);
+    if (EARLY) nx = load_pre2(a, gn * F + grp);
     const bool act = cur.ok && cur.len <= kSmallMax;
     const uint32_t len = act ? cur.len : 0u;
     const uint32_t npc = (len + 15) >> 4;             // ciphertext Poly1305 pieces
@@ -1855,11 +1891,11 @@ void k_open_fold_v3(DecodeArgs a) {
     if (CE_V3_PRIO) __builtin_amdgcn_s_setprio(CE_V3_PRIO);  // the decode's short dependent chains first
     if constexpr (GS) {
       decode_gset_lds<LPF>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, gsc, [&] {
-        if (!EARLY) nx = load_pre2(a, (g + 1) * F + grp);
+        if (!EARLY) nx = load_pre2(a, gn * F + grp);
       });
     } else {
       decode_fold<LPF, true, PN>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, S, [&] {
-        if (!EARLY) nx = load_pre2(a, (g + 1) * F + grp);
+        if (!EARLY) nx = load_pre2(a, gn * F + grp);
       });
     }
     if (CE_V3_PRIO) __builtin_amdgcn_s_setprio(0);
@@ -1868,6 +1904,17 @@ void k_open_fold_v3(DecodeArgs a) {
   if constexpr (GS) gsc.flush(a);
   else flush_pending<LPF>(a, sub, S.pslot, S.pbest);
   fails.flush(a);
+  if (a.stamps) {
+    const unsigned long long t_out = __builtin_amdgcn_s_memrealtime();
+    // HW_REG_HW_ID (wave slot, SIMD, CU, SH, SE, ...) and HW_REG_XCC_ID's low four bits
+    const unsigned long long hw = (uint32_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
+                                  ((unsigned long long)(uint32_t)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32);
+    if (lane == 0) {
+      unsigned long long* o = a.stamps + (uint64_t)kStampWords * blockIdx.x;
+      o[1] = t_out;
+      o[2] = hw;
+    }
+  }
 }
 
 // ----------------------------------------------------------------------------------------
@@ -2132,8 +2179,9 @@ hipError_t launch_open_fold_pn(hipStream_t s, const DecodeArgs& a, OpenLaunchLog
   if (!a.aux) return hipErrorInvalidValue;  // the v3 open needs the setup's PolyAux rows
   static const uint32_t res = resident_blocks(k_open_fold_v3<false, true, true>, 64);
   const dim3 grid(log.grid(std::min<uint32_t>((a.n + 3) / 4, res), "open_v3_pn"));
-  if (t0) hipExtLaunchKernelGGL((k_open_fold_v3<false, true, true>), grid, dim3(64), 0, s, t0, t1, 0u, a);
-  else hipLaunchKernelGGL((k_open_fold_v3<false, true, true>), grid, dim3(64), 0, s, a);
+  const DecodeArgs b = log.stamped(a, grid.x);
+  if (t0) hipExtLaunchKernelGGL((k_open_fold_v3<false, true, true>), grid, dim3(64), 0, s, t0, t1, 0u, b);
+  else hipLaunchKernelGGL((k_open_fold_v3<false, true, true>), grid, dim3(64), 0, s, b);
   return hipGetLastError();
 }
 
@@ -2143,8 +2191,9 @@ hipError_t launch_open_fold_gset(hipStream_t s, const DecodeArgs& a, OpenLaunchL
   if (!a.aux || !a.gs) return hipErrorInvalidValue;  // the setup's PolyAux rows, the hash tables
   static const uint32_t res = resident_blocks(k_open_fold_v3<false, true, false, true>, 64);
   const dim3 grid(log.grid(std::min<uint32_t>((a.n + 3) / 4, res), "open_v3_gset"));
-  if (t0) hipExtLaunchKernelGGL((k_open_fold_v3<false, true, false, true>), grid, dim3(64), 0, s, t0, t1, 0u, a);
-  else hipLaunchKernelGGL((k_open_fold_v3<false, true, false, true>), grid, dim3(64), 0, s, a);
+  const DecodeArgs b = log.stamped(a, grid.x);
+  if (t0) hipExtLaunchKernelGGL((k_open_fold_v3<false, true, false, true>), grid, dim3(64), 0, s, t0, t1, 0u, b);
+  else hipLaunchKernelGGL((k_open_fold_v3<false, true, false, true>), grid, dim3(64), 0, s, b);
   return hipGetLastError();
 }
 
@@ -2163,8 +2212,9 @@ hipError_t launch_open_fold_v2(hipStream_t s, const DecodeArgs& a, int files_per
     auto go = [&](auto kern, const char* key) {
       const uint32_t res = resident_blocks(kern, 64);
       const dim3 grid(log.grid(std::min<uint32_t>((a.n + 3) / 4, res), key));
-      if (t0) hipExtLaunchKernelGGL(kern, grid, dim3(64), 0, s, t0, t1, 0u, a);
-      else hipLaunchKernelGGL(kern, grid, dim3(64), 0, s, a);
+      const DecodeArgs b = log.stamped(a, grid.x);
+      if (t0) hipExtLaunchKernelGGL(kern, grid, dim3(64), 0, s, t0, t1, 0u, b);
+      else hipLaunchKernelGGL(kern, grid, dim3(64), 0, s, b);
     };
     switch (v3 & 3) {
       case 1: go(k_open_fold_v3<true, false>, "open_v3_p1e0"); break;

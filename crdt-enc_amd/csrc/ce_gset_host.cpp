@@ -801,6 +801,8 @@ int fold_batch(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32
   da.aux = ctx->poly_aux.as<PolyAux>();
   da.gs = g->fused.as<GsFused>();
   ctx->open_log.grid_cap = test_grid_cap();
+  ctx->open_log.stamps = test_wave_stamps(ctx);
+  ctx->open_log.stamp_waves = 0;  // this ingest's launches, if stamped, are the ones to read
   {
     hipEvent_t t0, t1;
     (void)ctx->tlaunch("open_fold_small", &t0, &t1);

@@ -149,7 +149,8 @@ struct ce_ctx {
   // batch scratch (device)
   ce::DevBuf params, status, counters, extra, multi, partials, large, out, apply, refold, miss,
       supported, blob, offs, nonces, out_offs, outer_ver, batch_counters, split, segrec, redo, heads,
-      poly_aux;  // PolyAux rows of the fused open (device_open_setup)
+      poly_aux,  // PolyAux rows of the fused open (device_open_setup)
+      stamps;    // CE_TEST_WAVE_STAMPS: k_open_fold_v3's wave stamps (never allocated in the product)
   // which open kernels the last launches took (ce_kernels.h); drained into a core's path counts
   ce::OpenLaunchLog open_log;
   ce::HostBuf h_counters, h_apply, h_stage, h_stage2, h_heads;
@@ -271,6 +272,11 @@ uint32_t grid_waves_for(uint32_t work);
 // open launchers (OpenLaunchLog.grid_cap) and grid_waves_for, so that a small batch runs every
 // persistent loop many times per wave.  Read per call, as CE_SEGDEC and CE_SPLIT.
 uint32_t test_grid_cap();
+// CE_TEST_WAVE_STAMPS=1 (tests and tools only; read per ingest, as CE_TEST_GRID_CAP): ctx's stamp
+// buffer, zeroed on ctx's stream, for OpenLaunchLog.stamps -- k_open_fold_v3's waves then record
+// when they entered and left their loops and where they ran (ce_ctx_wave_stamps copies them out).
+// Null when the variable is absent: the product's kernels get no buffer.
+unsigned long long* test_wave_stamps(ce_ctx* ctx);
 
 // ce_dma.cpp: device -> host copies on an SDMA engine (HSA), completion on a signal
 struct DmaD2H {

@@ -72,7 +72,8 @@ struct SegScratch {
 
 // One launch for an ingest's scratch initialisation (each hipMemsetAsync is its own blit
 // dispatch with its own gap): ranges of u32 words set to a value, and the 16-word counter block
-// zeroed with [5] (first failing index) and [13] (the gate's first gap) = UINT32_MAX.
+// zeroed with [5] (first failing index) and [13] (the gate's first gap) = UINT32_MAX, and the
+// fused open's ticket (kTicketWord, below) zeroed beside it.
 static constexpr int kMaxFill = 10;
 struct FillRange {
   uint32_t* p;
@@ -165,7 +166,31 @@ struct DecodeArgs {
                                 // probe (lookup_slot1)
   DsFuse ds;                    // launch_open_small_v2: Orswot ops decoded in the open (ds.on)
   const PolyAux* aux;           // fused open (k_open_fold_v3): the setup's per-file constants
+  unsigned long long* stamps;   // null in the product.  Tests and tools (CE_TEST_WAVE_STAMPS):
+                                // k_open_fold_v3's wave b writes kStampWords words at
+                                // stamps[kStampWords * b] (ce_ctx_wave_stamps)
 };
+// k_open_fold_v3's ticket: the word of the counter block its waves draw their chunks of file groups
+// from (ce_fused.hip).  Words 0..15 are all taken ([6] is the setup's partial-slot allocator), so
+// the ticket has a 128-byte line of the 256-byte block to itself; k_fill zeroes it with the block,
+// and a caller that launches the kernel again over the same block zeroes it before that launch.
+static constexpr uint32_t kTicketWord = 32;
+// k_open_fold_v3's schedule (ce_fused.hip; DESIGN.md section 7 has the settings measured): file groups per
+// drawn chunk, and the percentage of a wave's even share it takes as a fixed run first.  At 1M
+// files and 2048 waves: 64 groups fixed, then 32K tickets (same-address atomics cost ~10 ns each;
+// chunks of 1 group, 131K tickets, ran slower than fixed runs alone)
+#ifndef CE_DYN_CHUNK
+#define CE_DYN_CHUNK 4u
+#endif
+#ifndef CE_DYN_STATIC_PCT
+#define CE_DYN_STATIC_PCT 50u
+#endif
+static_assert(CE_DYN_CHUNK >= 1 && CE_DYN_CHUNK <= 64 && CE_DYN_STATIC_PCT <= 100, "k_open_fold_v3 schedule");
+// a wave's stamps: [0] the 100 MHz reference clock when it entered its loop, [1] when it left it,
+// [2] HW_ID | XCC_ID << 32, [3] left zero by the kernel: ce_ctx_wave_stamps puts the build's
+// schedule there, CE_DYN_CHUNK | CE_DYN_STATIC_PCT << 32
+static constexpr uint32_t kStampWords = 4;
+static constexpr uint32_t kStampWaves = 16384;  // a launch of more blocks is not stamped
 hipError_t launch_decode_dots(hipStream_t s, const DecodeArgs& a, uint32_t grid_waves);
 // the same for a PNCounter core: Vec<pncounter::Op<Uuid>>, a.batch in two planes (Pos at [slot],
 // Neg at [slot + mask + 1])
@@ -208,6 +233,17 @@ struct OpenLaunchLog {
     if (grid_cap == 0 || blocks <= grid_cap) return blocks;
     note("open_grid_capped");
     return grid_cap;
+  }
+  // the test-only CE_TEST_WAVE_STAMPS, set by the caller per ingest as grid_cap: kStampWaves *
+  // kStampWords words of device memory for k_open_fold_v3's waves, or null (the product);
+  // stamp_waves: the grid of the last launch that was stamped
+  unsigned long long* stamps = nullptr;
+  uint32_t stamp_waves = 0;
+  DecodeArgs stamped(const DecodeArgs& a, uint32_t blocks) {
+    DecodeArgs b = a;
+    b.stamps = blocks <= kStampWaves ? stamps : nullptr;
+    stamp_waves = b.stamps ? blocks : 0;  // a launch that is not stamped leaves none to read
+    return b;
   }
 };
 

@@ -1393,6 +1393,7 @@ __global__ void k_fill(FillArgs a) {
   if ((int)r == a.n) {  // the counter block
     if (blockIdx.x == 0 && threadIdx.x < 16)
       a.counters[threadIdx.x] = (threadIdx.x == 5 || threadIdx.x == 13) ? 0xffffffffu : 0u;
+    if (blockIdx.x == 0 && threadIdx.x == kTicketWord) a.counters[kTicketWord] = 0u;  // k_open_fold_v3's ticket
     return;
   }
   const FillRange f = a.r[r];

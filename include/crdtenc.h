@@ -88,6 +88,17 @@ void ce_ctx_timing_reset(ce_ctx *ctx);
  * * 2 uint64).  Asynchronous; at most 4096 blocks, samples * ticks <= 10^8 (1 s). */
 int ce_ctx_clock_probe(ce_ctx *ctx, void *hip_stream, uint64_t *d_out, uint32_t blocks,
                        uint32_t samples, uint32_t ticks);
+/* Diagnostics (tests and tools; no reference counterpart): with CE_TEST_WAVE_STAMPS=1 in the
+ * environment of an ingest, every wave of its fused open kernel (one wave per block) records four
+ * uint64: the 100 MHz reference clock when it entered and when it left its loop over the files, its
+ * hardware id (HW_ID | XCC_ID << 32: wave slot, SIMD, CU, shader engine, XCD) and a spare word.
+ * Copies the words of the last launch of that kernel by the context's last ingest to `out` (host
+ * memory, cap_waves * 4 uint64; at most cap_waves waves) and stores its wave count in *n_waves (0:
+ * the ingest ran without the variable, or opened its files with another kernel).  The fourth word
+ * of every row is filled here with the schedule the library was built with: file groups per drawn
+ * chunk | percent of a wave's share taken as its fixed run << 32.
+ * Synchronizes the context stream. */
+int ce_ctx_wave_stamps(ce_ctx *ctx, uint64_t *out, uint32_t cap_waves, uint32_t *n_waves);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Cryptor: XChaCha20-Poly1305 EncHandler on the GPU                                          */
