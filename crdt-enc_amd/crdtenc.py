@@ -66,6 +66,8 @@ EXPORTS = [
     "ce_core_set_contains_device", "ce_core_set_contains", "ce_core_set_len", "ce_core_set_members_device",
     "ce_core_counter_read", "ce_core_clock_get", "ce_core_read_clock", "ce_core_orswot_member_clocks",
     "ce_core_mvreg_read",
+    "ce_ctx_prim_excl_sum_u32", "ce_ctx_prim_excl_max_by_key", "ce_ctx_prim_sort_pairs_u32",
+    "ce_ctx_prim_sort_pairs_u64",
 ]
 
 
@@ -431,6 +433,34 @@ class Context:
             self.check(lib().ce_ctx_wave_stamps(self.p, ctypes.c_void_p(out.ctypes.data), ctypes.c_uint32(n.value),
                                                 ctypes.byref(n)), "wave_stamps")
         return out[:n.value]
+
+    # Diagnostics: the device primitives (ce_ctx_prim_*), each through the function the product
+    # calls, over 0xFF-filled scratch.  Pointers are device addresses (0 = null) of n items.
+    def prim_excl_sum_u32(self, in_ptr, out_ptr, n):
+        """out[i] = sum of in[0..i) mod 2^32 (ds_excl_sum_u32)"""
+        self.check(lib().ce_ctx_prim_excl_sum_u32(self.p, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr),
+                                                  ctypes.c_uint32(n)), "prim_excl_sum_u32")
+
+    def prim_excl_max_by_key(self, keys_ptr, vals_ptr, out_ptr, n):
+        """out[i] = max of the u64 vals before i in its run of adjacent equal u32 keys, 0 at a run's
+        first item (ds_excl_max_by_key)"""
+        self.check(lib().ce_ctx_prim_excl_max_by_key(self.p, ctypes.c_void_p(keys_ptr), ctypes.c_void_p(vals_ptr),
+                                                     ctypes.c_void_p(out_ptr), ctypes.c_uint32(n)),
+                   "prim_excl_max_by_key")
+
+    def _prim_sort(self, f, what, kin_ptr, kout_ptr, vin_ptr, vout_ptr, n, bits):
+        self.check(f(self.p, ctypes.c_void_p(kin_ptr), ctypes.c_void_p(kout_ptr), ctypes.c_void_p(vin_ptr),
+                     ctypes.c_void_p(vout_ptr), ctypes.c_uint32(n), ctypes.c_int(bits)), what)
+
+    def prim_sort_pairs_u32(self, kin_ptr, kout_ptr, vin_ptr, vout_ptr, n, bits):
+        """Stable sort of (u32 key, u32 value) pairs by the keys' low `bits` bits (ds_sort_pairs_u32)"""
+        self._prim_sort(lib().ce_ctx_prim_sort_pairs_u32, "prim_sort_pairs_u32", kin_ptr, kout_ptr, vin_ptr,
+                        vout_ptr, n, bits)
+
+    def prim_sort_pairs_u64(self, kin_ptr, kout_ptr, vin_ptr, vout_ptr, n, bits):
+        """The same over u64 keys (sort_pairs_u64; bits = 0: all 64)"""
+        self._prim_sort(lib().ce_ctx_prim_sort_pairs_u64, "prim_sort_pairs_u64", kin_ptr, kout_ptr, vin_ptr,
+                        vout_ptr, n, bits)
 
     # ---- Cryptor ----
     def gen_key(self):

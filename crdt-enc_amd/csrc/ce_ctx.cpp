@@ -8,6 +8,8 @@
 #include <algorithm>
 #include <cstdio>
 
+#include "ce_dotset.h"
+#include "ce_dotset_io.h"
 #include "ce_internal.h"
 
 namespace ce {
@@ -299,6 +301,29 @@ int seal_one(ce_ctx* ctx, const KeyRef& key, const uint8_t* outer_version, const
 
 using namespace ce;
 
+// ce_ctx_prim_*: one device primitive on the context stream, through the function the product
+// calls, over scratch of the queried size filled with 0xFF bytes first -- what a primitive needs
+// zero it has to zero itself.  call(tmp, tb): the primitive's two-call form.
+template <typename F>
+static int prim_run(ce_ctx* c, const char* what, bool null_arg, F&& call) {
+  if (!c) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  (void)hipSetDevice(c->device);
+  size_t tb = 0;
+  hipError_t e = call(nullptr, tb);
+  if (e == hipErrorInvalidValue) return c->fail(CE_ERR_INVALID_ARG, std::string(what) + ": more items than the primitive takes");
+  if (e != hipSuccess) return c->hip_fail(e, what);
+  if (null_arg) return c->fail(CE_ERR_INVALID_ARG, std::string(what) + ": null pointer");
+  void* tmp = nullptr;
+  if ((e = hipMalloc(&tmp, tb)) != hipSuccess) return c->hip_fail(e, what);
+  if ((e = hipMemsetAsync(tmp, 0xFF, tb, c->stream)) == hipSuccess) e = call(tmp, tb);
+  const hipError_t w = hipStreamSynchronize(c->stream);  // the launches read tmp: wait before the free
+  if (e == hipSuccess) e = w;
+  (void)hipFree(tmp);
+  if (e == hipErrorInvalidValue) return c->fail(CE_ERR_INVALID_ARG, std::string(what) + ": invalid value");
+  return e == hipSuccess ? CE_OK : c->hip_fail(e, what);
+}
+
 extern "C" {
 
 const char* ce_status_str(int s) {
@@ -452,6 +477,34 @@ int ce_ctx_wave_stamps(ce_ctx* c, uint64_t* out, uint32_t cap_waves, uint32_t* n
   // the schedule this library was built with, for a caller that places its cases by it
   for (uint32_t i = 0; i < k; i++) out[(size_t)kStampWords * i + 3] = (uint64_t)CE_DYN_CHUNK | ((uint64_t)CE_DYN_STATIC_PCT << 32);
   return CE_OK;
+}
+
+int ce_ctx_prim_excl_sum_u32(ce_ctx* c, const uint32_t* d_in, uint32_t* d_out, uint32_t n) {
+  return prim_run(c, "prim excl_sum_u32", n && (!d_in || !d_out), [&](void* tmp, size_t& tb) {
+    return ds_excl_sum_u32(tmp, tb, d_in, d_out, n, c->stream);
+  });
+}
+
+int ce_ctx_prim_excl_max_by_key(ce_ctx* c, const uint32_t* d_keys, const uint64_t* d_vals, uint64_t* d_out, uint32_t n) {
+  return prim_run(c, "prim excl_max_by_key", n && (!d_keys || !d_vals || !d_out), [&](void* tmp, size_t& tb) {
+    return ds_excl_max_by_key(tmp, tb, d_keys, reinterpret_cast<const unsigned long long*>(d_vals),
+                              reinterpret_cast<unsigned long long*>(d_out), n, c->stream);
+  });
+}
+
+int ce_ctx_prim_sort_pairs_u32(ce_ctx* c, const uint32_t* d_kin, uint32_t* d_kout, const uint32_t* d_vin,
+                               uint32_t* d_vout, uint32_t n, int bits) {
+  return prim_run(c, "prim sort_pairs_u32", n && (!d_kin || !d_kout || !d_vin || !d_vout), [&](void* tmp, size_t& tb) {
+    return ds_sort_pairs_u32(tmp, tb, d_kin, d_kout, d_vin, d_vout, n, bits, c->stream);
+  });
+}
+
+int ce_ctx_prim_sort_pairs_u64(ce_ctx* c, const uint64_t* d_kin, uint64_t* d_kout, const uint32_t* d_vin,
+                               uint32_t* d_vout, uint32_t n, int bits) {
+  return prim_run(c, "prim sort_pairs_u64", n && (!d_kin || !d_kout || !d_vin || !d_vout), [&](void* tmp, size_t& tb) {
+    return sort_pairs_u64(tmp, tb, reinterpret_cast<const unsigned long long*>(d_kin),
+                          reinterpret_cast<unsigned long long*>(d_kout), d_vin, d_vout, n, bits, c->stream);
+  });
 }
 
 int ce_ctx_timing_read(ce_ctx* c, const char* kernel, double* total_ms, uint64_t* launches) {

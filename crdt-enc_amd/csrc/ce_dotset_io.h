@@ -59,6 +59,9 @@ struct OrswotSerScratch {
 // (key_bits <= 64).  State (u32 words, zero before the first sort; the sorts keep it so):
 // hist [2][8 replicas][kSortMaxPlaces][256] | ticket [kSortMaxPlaces] | pad, then from word
 // kSortStateHead: look [places][tiles][256]
+// The most items one sort takes: a look-back word holds a tile's count or prefix in its low 30
+// bits.  launch_ser_sort and sort_pairs_* return hipErrorInvalidValue past it, the size query too.
+static constexpr uint32_t kSortMaxItems = (1u << 30) - 1;
 static constexpr uint32_t kSortMaxPlaces = 8;
 static constexpr uint32_t kSortStateHead = 2 * 8 * kSortMaxPlaces * 256 + 64;
 struct SerSortArgs {

@@ -863,8 +863,11 @@ static size_t cached_tmp_bytes(uint32_t n, size_t (*raw)(uint32_t), std::map<uin
 
 static size_t ser_tmp_bytes_raw(uint32_t n) {
   size_t a = 0, b = 0, c = 0;
-  (void)sort_pairs_u32(nullptr, a, nullptr, nullptr, nullptr, nullptr, n, 32, nullptr);
-  (void)sort_pairs_u64(nullptr, b, nullptr, nullptr, nullptr, nullptr, n, 64, nullptr);
+  // (n is a power of two at or above the pairs: the sorts take at most kSortMaxItems, and refuse
+  // the query past it)
+  const uint32_t ns = std::min(n, kSortMaxItems);
+  (void)sort_pairs_u32(nullptr, a, nullptr, nullptr, nullptr, nullptr, ns, 32, nullptr);
+  (void)sort_pairs_u64(nullptr, b, nullptr, nullptr, nullptr, nullptr, ns, 64, nullptr);
   (void)ds_excl_sum_u32(nullptr, c, nullptr, nullptr, n, nullptr);
   return std::max(std::max(a, b), c) + 256;
 }

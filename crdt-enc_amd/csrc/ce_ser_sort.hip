@@ -29,7 +29,10 @@ constexpr int kSortPerLane = 16;
 constexpr uint32_t kSortTile = kSortThreads * kSortPerLane;  // 4096
 constexpr int kDigitBits = 8;
 constexpr uint32_t kDigits = 1u << kDigitBits;
+// a look-back word: two flag bits over a 30-bit count.  A prefix is at most n, so a sort of more
+// than kCountMask items would carry into the flags: the launchers reject it (kSortMaxItems)
 constexpr uint32_t kFlagAgg = 1u << 30, kFlagInc = 2u << 30, kCountMask = (1u << 30) - 1;
+static_assert(kCountMask == kSortMaxItems, "the launchers' item limit is the look-back count's width");
 static_assert(kDigits == kSortThreads, "one lane per digit in the tile bookkeeping");
 constexpr int kLookWindow = 16;
 // the histogram in kHistReps replicas (block b adds into replica b % kHistReps, ~ its XCD): a
@@ -276,6 +279,7 @@ __global__ void __launch_bounds__(kSortThreads) k_sort_zero(uint32_t* hist) {
 template <typename K>
 hipError_t sort_pairs_t(void* tmp, size_t& tb, const K* kin, K* kout, const uint32_t* vin, uint32_t* vout,
                         uint32_t n, int bits, hipStream_t s) {
+  if (n > kCountMask) return hipErrorInvalidValue;
   // scratch: sort state | keys x 2 | u64 values x 2 (the passes' ping-pong buffers)
   const uint32_t tiles = (n + kSortTile - 1) / kSortTile;
   const size_t sw = ((size_t)kSortStateHead + (size_t)kSortMaxPlaces * tiles * kDigits) * 4;
@@ -329,6 +333,7 @@ hipError_t launch_ser_sort(hipStream_t s, const SerSortArgs& in, void* const kbu
                            unsigned long long* const vbuf[2]) {
   SerSortArgs a = in;
   if (a.n == 0) return hipSuccess;
+  if (a.n > kCountMask) return hipErrorInvalidValue;
   a.tiles = ser_sort_tiles(a.n);
   a.places = (uint32_t)((a.key_bits + kDigitBits - 1) / kDigitBits);
   if (a.places == 0) a.places = 1;

@@ -99,6 +99,26 @@ int ce_ctx_clock_probe(ce_ctx *ctx, void *hip_stream, uint64_t *d_out, uint32_t 
  * chunk | percent of a wave's share taken as its fixed run << 32.
  * Synchronizes the context stream. */
 int ce_ctx_wave_stamps(ce_ctx *ctx, uint64_t *out, uint32_t cap_waves, uint32_t *n_waves);
+/* Diagnostics (tests and tools; no reference counterpart): the device primitives under the dot-set
+ * folds, the Orswot serializer and the GSet state writer, each run once on the context stream by the
+ * function the product calls, over scratch of the size it asks for that is filled with 0xFF bytes
+ * first.  All pointers are device memory of n items; inputs are not modified and outputs may not
+ * alias them.  n = 0 writes nothing.  Each call allocates and frees its scratch and synchronizes the
+ * context stream.
+ *   excl_sum_u32     d_out[i] = sum of d_in[0..i) mod 2^32
+ *   excl_max_by_key  d_out[i] = max of d_vals[j] over the j < i in i's run of adjacent equal
+ *                    d_keys (0 at a run's first item)
+ *   sort_pairs_*     (d_kout, d_vout) = the pairs ordered by key, equal keys in input order; keys
+ *                    must fit in `bits` bits (0, or more than the key's width: the full width).
+ *                    More than 2^30 - 1 items: CE_ERR_INVALID_ARG, nothing launched, no memory
+ *                    touched. */
+int ce_ctx_prim_excl_sum_u32(ce_ctx *ctx, const uint32_t *d_in, uint32_t *d_out, uint32_t n);
+int ce_ctx_prim_excl_max_by_key(ce_ctx *ctx, const uint32_t *d_keys, const uint64_t *d_vals,
+                                uint64_t *d_out, uint32_t n);
+int ce_ctx_prim_sort_pairs_u32(ce_ctx *ctx, const uint32_t *d_kin, uint32_t *d_kout,
+                               const uint32_t *d_vin, uint32_t *d_vout, uint32_t n, int bits);
+int ce_ctx_prim_sort_pairs_u64(ce_ctx *ctx, const uint64_t *d_kin, uint64_t *d_kout,
+                               const uint32_t *d_vin, uint32_t *d_vout, uint32_t n, int bits);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Cryptor: XChaCha20-Poly1305 EncHandler on the GPU                                          */
