@@ -6,7 +6,8 @@
 //                     flags by a stable sort + segmented max scan, pair-table max-insert,
 //                     removal thresholds; MVReg: maximal-clock rounds)
 //   read_remote_states (lib.rs:401-469)  GPU open -> host flatten of StateWrapper<S> -> per-pair
-//                     Orswot::merge kernel (MVReg: survivor rounds with earlier-wins ties)
+//                     Orswot::merge kernel (MVReg: survivor rounds with earlier-wins ties; a vals
+//                     list that is no antichain of non-empty clocks merges on the host)
 //   apply_ops         (lib.rs:666-722)   host parse of the local ops -> the same GPU fold
 //
 // The deferred removals of an Orswot and the values of an MVReg are small and live on the host;
@@ -59,6 +60,10 @@ struct DsState {
   std::map<IdDots, std::set<uint64_t>> deferred;  // removal clock -> members (HashMap in crdts)
   // MVReg
   std::vector<std::pair<IdDots, uint64_t>> vals;
+  // vals is not an antichain of non-empty clocks (only a state file not in the writer's form
+  // can make it so): the survivor rounds do not state MVReg::merge / apply for such a list, so
+  // merges and op folds run on the host (mv_host_merge / mv_host_apply) until it is one again
+  bool mv_irregular = false;
   std::vector<std::vector<uint8_t>> ser_parts;  // per-thread entry writer output (reused)
   // scratch
   DevBuf cnt, ops[10], applied, sort_keys, sort_perm, sort_keys2, sort_perm2, ctr_sorted, excl,
@@ -885,6 +890,7 @@ int mvreg_survivors(ce_core* c, uint32_t n, bool later_wins, std::vector<uint32_
   hipStream_t s = ctx->stream;
   out->clear();
   if (n == 0) return CE_OK;
+  c->path_counts["mv_device_rounds"]++;
   int rc;
   if ((rc = ensure_clock(c))) return rc;
   DsOps o = ops_view(d);
@@ -969,6 +975,116 @@ int mvreg_commit(ce_core* c, uint32_t K, uint32_t total, bool later_wins) {
     nv.push_back(std::move(v));
   }
   d->vals = std::move(nv);
+  return CE_OK;
+}
+
+// The host route of an MVReg whose values (this core's or a state file's) are not an antichain
+// of non-empty clocks: crdts' MVReg::merge and MVReg::apply statement by statement (as
+// ce_keys.cpp's MVRegT::merge), on clocks by actor id, ids ascending.
+using MvVals = std::vector<std::pair<IdDots, uint64_t>>;
+
+// a <= b (PartialOrd): every dot of a is covered by b
+bool mv_le(const IdDots& a, const IdDots& b) {
+  size_t j = 0;
+  for (auto& x : a) {
+    while (j < b.size() && b[j].first < x.first) j++;
+    if (j == b.size() || b[j].first != x.first || b[j].second < x.second) return false;
+  }
+  return true;
+}
+
+bool mv_lt(const IdDots& a, const IdDots& b) { return a != b && mv_le(a, b); }
+
+// every clock non-empty and none <= another (equal clocks included)
+bool mv_regular(const MvVals& v) {
+  for (size_t i = 0; i < v.size(); i++) {
+    if (v[i].first.empty()) return false;
+    for (size_t j = 0; j < v.size(); j++)
+      if (i != j && mv_le(v[i].first, v[j].first)) return false;
+  }
+  return true;
+}
+
+void mvreg_host_merge(ce_core* c, const MvVals& other) {
+  DsState* d = c->ds;
+  MvVals kept;
+  for (auto& x : d->vals) {
+    bool dominated = false;
+    for (auto& y : other) dominated |= mv_lt(x.first, y.first);
+    if (!dominated) kept.push_back(x);
+  }
+  MvVals add;
+  for (auto& y : other) {
+    bool dominated = false, dup = false;
+    for (auto& x : kept) {
+      dominated |= mv_lt(y.first, x.first);
+      dup |= y.first == x.first;
+    }
+    if (!dominated && !dup) add.push_back(y);
+  }
+  kept.insert(kept.end(), add.begin(), add.end());
+  d->vals.swap(kept);
+  d->mv_irregular = !mv_regular(d->vals);
+  c->path_counts["mv_host_merge"]++;
+}
+
+// MVReg::apply of the puts in order
+void mvreg_host_apply(ce_core* c, const MvVals& puts) {
+  DsState* d = c->ds;
+  for (auto& p : puts) {
+    if (p.first.empty()) continue;
+    MvVals kept;
+    for (auto& x : d->vals)
+      if (!mv_le(x.first, p.first)) kept.push_back(std::move(x));
+    bool seen = false;
+    for (auto& x : kept) seen |= mv_lt(p.first, x.first);
+    if (!seen) kept.push_back(p);
+    d->vals.swap(kept);
+  }
+  d->mv_irregular = !mv_regular(d->vals);
+  c->path_counts["mv_host_apply"]++;
+}
+
+// the puts at candidate indices [K, total) of the op columns (device) -> host, in order
+int fetch_puts(ce_core* c, uint32_t K, uint32_t total, MvVals* out) {
+  out->clear();
+  if (total <= K) return CE_OK;
+  DsOps o = ops_view(c->ds);
+  hipStream_t s = c->ctx->stream;
+  const uint32_t n = total - K;
+  std::vector<uint32_t> cb(n + 1);
+  std::vector<unsigned long long> val(n);
+  hipError_t e;
+  if ((e = hipMemcpyAsync(cb.data(), o.rm_cbeg + K, (n + 1) * 4ull, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(val.data(), o.put_val + K, n * 8ull, hipMemcpyDeviceToHost, s)) ||
+      (e = stream_wait(s)))
+    return c->ctx->hip_fail(e, "puts");
+  for (uint32_t i = 0; i < n; i++)
+    if (cb[i + 1] < cb[i]) return c->ctx->fail(CE_ERR_DEVICE, "put clock offsets not ascending");
+  const uint32_t k = cb[n] - cb[0];
+  std::vector<uint32_t> act(k);
+  std::vector<unsigned long long> ctr(k);
+  if (k && ((e = hipMemcpyAsync(act.data(), o.rmc_actor + cb[0], k * 4ull, hipMemcpyDeviceToHost, s)) ||
+            (e = hipMemcpyAsync(ctr.data(), o.rmc_ctr + cb[0], k * 8ull, hipMemcpyDeviceToHost, s)) ||
+            (e = stream_wait(s))))
+    return c->ctx->hip_fail(e, "puts");
+  out->resize(n);
+  for (uint32_t i = 0; i < n; i++) {
+    auto& v = (*out)[i];
+    for (uint32_t j = cb[i] - cb[0]; j < cb[i + 1] - cb[0]; j++) v.first.push_back({act[j], ctr[j]});
+    std::sort(v.first.begin(), v.first.end());
+    v.second = val[i];
+  }
+  return CE_OK;
+}
+
+// the op routes' last step: the survivor rounds, or MVReg::apply on the host while vals is irregular
+int mvreg_fold_ops(ce_core* c, uint32_t K, uint32_t total) {
+  if (!c->ds->mv_irregular) return mvreg_commit(c, K, total, true);
+  MvVals puts;
+  int rc = fetch_puts(c, K, total, &puts);
+  if (rc) return rc;
+  mvreg_host_apply(c, puts);
   return CE_OK;
 }
 
@@ -1074,6 +1190,7 @@ int resolve_host_decode(ce_core* c, uint32_t n, std::vector<int32_t>* st) {
   hipError_t e;
   for (uint32_t i = 0; i < n; i++) {
     if ((*st)[i] != kStatusHostDecode) continue;
+    c->path_counts["ds_host_decode_files"]++;
     FileParams P;
     if ((e = hipMemcpy(&P, ctx->params.as<FileParams>() + i, sizeof P, hipMemcpyDeviceToHost)))
       return ctx->hip_fail(e, "host decode");
@@ -1163,6 +1280,7 @@ int ds_reset(ce_core* c) {
   d->settle_d0.clear();
   d->deferred.clear();
   d->vals.clear();
+  d->mv_irregular = false;
   hipError_t e;
   const FillRange clock_zero{d->clock.as<uint32_t>(), 2ull * d->clock_cap, 0u};
   if (c->kind == CE_STATE_ORSWOT)  // the clock cleared by the tables' fill launch
@@ -1469,7 +1587,7 @@ int ds_ingest_ops(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uin
     rc = orswot_fold(c, tot, tot.v[kCntRmM] * std::max<uint64_t>(1, kmax.v[kCntRmC]), d->adds_contig);
     d->adds_contig = false;  // describes this batch's columns only
   } else {
-    rc = mvreg_commit(c, (uint32_t)base.v[kCntRm], (uint32_t)tot.v[kCntRm], true);
+    rc = mvreg_fold_ops(c, (uint32_t)base.v[kCntRm], (uint32_t)tot.v[kCntRm]);
   }
   if (rc) return rc;
   // 7) next_op_versions (lib.rs:537-538) and the gap error (lib.rs:527-531).  The decode's misses
@@ -1727,12 +1845,23 @@ int orswot_merge_cols(ce_core* c, const IdDots& oclock,
 int mvreg_merge_one(ce_core* c, const HostState& hs) {
   DsState* d = c->ds;
   int rc;
-  HostCols hc;
-  vals_cols(d, &hc);
-  const uint32_t K = (uint32_t)d->vals.size();
+  // MVReg::merge as survivor rounds needs both sides' vals to be antichains of non-empty clocks
+  // (a writer built on crdts produces no other): anything else merges on the host, exactly
+  MvVals other;
   for (auto& v : hs.vals) {
     IdDots id;
     if ((rc = id_dots(c, v.first, &id))) return rc;
+    other.push_back({std::move(id), v.second});
+  }
+  if (d->mv_irregular || !mv_regular(other)) {
+    mvreg_host_merge(c, other);
+    return CE_OK;
+  }
+  HostCols hc;
+  vals_cols(d, &hc);
+  const uint32_t K = (uint32_t)d->vals.size();
+  for (auto& v : other) {
+    const IdDots& id = v.first;
     hc.rm_cbeg.push_back((uint32_t)hc.rmc_actor.size());
     hc.rm_mbeg.push_back(0);
     for (auto& x : id) { hc.rmc_actor.push_back(x.first); hc.rmc_ctr.push_back(x.second); }
@@ -2412,7 +2541,7 @@ int ds_apply_local_ops(ce_core* c, const uint8_t* ops, size_t len) {
     }
     return orswot_fold(c, tot, items, false);
   }
-  return mvreg_commit(c, (uint32_t)base.v[kCntRm], (uint32_t)tot.v[kCntRm], true);
+  return mvreg_fold_ops(c, (uint32_t)base.v[kCntRm], (uint32_t)tot.v[kCntRm]);
 }
 
 // Compaction of an Orswot state without bringing the entries to the host: the clear text

@@ -15,6 +15,12 @@ Merging a state O (Orswot::merge): per (m, a) with s = cur, t = O's value,
   r = max(s if s == t, s if s > O.C[a], t if t > C[a]); then kills by D + O.D; C = max; D filtered.
 MVReg: survivors = maximal put clocks; among equal clocks the latest applied op (merge: the
 earliest value) wins; survivors keep their insertion order.
+Precondition of the MVReg forms: the current `vals` (and, for the merge form, the other state's)
+is an antichain of non-empty clocks -- no clock empty, equal to or below another -- as every
+state a crdts writer serializes is.  Outside it neither form is MVReg::merge / MVReg::apply
+(sequential apply keeps a dominated value that no op covers; merge keeps both of two equal clocks
+of one side): tests/test_mvreg_cases_model.py asserts the difference on family F of
+tests/mvreg_cases.py, and ce_dotset_host.cpp takes its host route there.
 """
 from oracle import crdts as C
 
