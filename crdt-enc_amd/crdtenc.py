@@ -27,6 +27,7 @@ ERR_OP_VERSION, ERR_SHARD = 13, 69
 SHARD_BAD, SHARD_GAP, SHARD_E0_MISMATCH = 1, 2, 4
 STATE_VCLOCK, STATE_GCOUNTER, STATE_ORSWOT, STATE_MVREG, STATE_PNCOUNTER = 0, 1, 2, 3, 4
 STATE_GSET = 5
+STATE_LWWREG = 6
 OPEN_CREATE, COMPACT_INGEST_FORMAT, OPEN_MULTI_KEY = 1, 2, 4
 
 CORE_VERSION = bytes.fromhex("e834d789101b463498239de990a9051f")   # crdt-enc/src/lib.rs:26
@@ -65,7 +66,7 @@ EXPORTS = [
     "ce_core_gset_ingest_ops_device_sharded", "ce_core_gset_pending_members", "ce_core_gset_pending_commit",
     "ce_core_set_contains_device", "ce_core_set_contains", "ce_core_set_len", "ce_core_set_members_device",
     "ce_core_counter_read", "ce_core_clock_get", "ce_core_read_clock", "ce_core_orswot_member_clocks",
-    "ce_core_mvreg_read",
+    "ce_core_mvreg_read", "ce_core_lwwreg_read",
     "ce_ctx_prim_excl_sum_u32", "ce_ctx_prim_excl_max_by_key", "ce_ctx_prim_sort_pairs_u32",
     "ce_ctx_prim_sort_pairs_u64",
 ]
@@ -700,7 +701,7 @@ class Keys:
 
 class Core:
     """Core<S> for S in {VClock<Uuid>, GCounter<Uuid>, Orswot<u64, Uuid>, MVReg<u64, Uuid>,
-    PNCounter<Uuid>, GSet<u64>} (crdt-enc/src/lib.rs)."""
+    PNCounter<Uuid>, GSet<u64>, LWWReg<u64, u64>} (crdt-enc/src/lib.rs)."""
 
     def __init__(self, ctx, kind=STATE_GCOUNTER, supported=(), current_data_version=None,
                  local_path=None, remote_path=None, flags=0):
@@ -1146,6 +1147,12 @@ class Core:
         self.ctx.check(lib().ce_core_mvreg_read(self.p, ctypes.byref(b)), "mvreg_read")
         d = _take(b)
         return list(struct.unpack("<%dQ" % (len(d) // 8), d))
+
+    def lwwreg_read(self):
+        """(val, marker) of the committed LWWReg."""
+        v, m = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.ctx.check(lib().ce_core_lwwreg_read(self.p, ctypes.byref(v), ctypes.byref(m)), "lwwreg_read")
+        return v.value, m.value
 
     def writer_versions(self, actors):
         import numpy as np

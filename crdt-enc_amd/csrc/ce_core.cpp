@@ -2,7 +2,8 @@
 // batch engine.  S = VClock<Uuid> / GCounter<Uuid> / PNCounter<Uuid> live here; S = Orswot<u64, Uuid> /
 // MVReg<u64, Uuid> (the dot-set kinds) dispatch to ce_dotset_host.cpp, S = GSet<u64> to
 // ce_gset_host.cpp (its members live in a device hash set; the actor table and next_op_versions
-// below are shared).
+// below are shared), S = LWWReg<u64, u64> to ce_lww_host.cpp (the register is two host words; its
+// op files are decoded in the fused open into per-file records).
 //
 // State layout: a host-built open-addressing actor table (UUID -> dense slot) mirrored in HBM;
 // the CRDT state (VClock dots / GCounter.inner) is a dense u64[cap] max-register array in HBM
@@ -157,13 +158,15 @@ bool read_vclock(Rd& r, Dots* out) {
 
 // StateWrapper<S> { next_op_versions: VClock, state: S } (lib.rs:739-743)
 // stn (PNCounter): the n counter's dots; state = { p: GCounter, n: GCounter }
-// members (GSet): the `value` form, state = { value: BTreeSet<u64> }
+// members (GSet): the `value` form, state = { value: BTreeSet<u64> }; (LWWReg): one (val, marker)
+// pair appended per state, state = { val, marker }
 bool read_state_wrapper(const uint8_t* p, size_t n, int kind, Dots* nov, Dots* st, Dots* stn,
                         std::vector<uint64_t>* members = nullptr) {
   Rd r{p, n, 0};
   return read_struct(r, {"next_op_versions", "state"}, [&](int f, Rd& q) {
     if (f == 0) return read_vclock(q, nov);
     if (kind == CE_STATE_GSET) return read_gset_state(q, members);
+    if (kind == CE_STATE_LWWREG) return read_lww_state(q, members);
     if (kind == CE_STATE_PNCOUNTER)
       return read_struct(q, {"p", "n"}, [&](int g, Rd& q2) {
         return read_struct(q2, {"inner"}, [&](int, Rd& q3) { return read_vclock(q3, g == 0 ? st : stn); });
@@ -454,11 +457,13 @@ int serialize_state(ce_core* c, std::vector<uint8_t>* out, bool head_only = fals
                     const uint8_t* prefix16 = nullptr) {
   if (is_dotset_kind(c->kind)) return ds_serialize(c, out);
   std::vector<uint64_t> st;
-  int rc = c->kind == CE_STATE_GSET ? CE_OK : download_state(c, &st);  // (GSet: no dense state)
+  const bool lww = c->kind == CE_STATE_LWWREG;
+  int rc = c->kind == CE_STATE_GSET || lww ? CE_OK : download_state(c, &st);  // (GSet, LWWReg: no dense state)
   if (rc) return rc;
   ensure_sorted(c);
   const std::vector<uint32_t>& slots = c->sorted_slots;
-  if (c->kind == CE_STATE_GSET) {  // next_op_versions as below, then { value: the sorted members }
+  if (c->kind == CE_STATE_GSET || lww) {  // next_op_versions as below, then { value: the sorted members }
+                                          // or { val, marker }
     size_t n_nov = 0;
     for (uint32_t s : slots) n_nov += c->nov[s] != 0;
     Wr w;
@@ -473,6 +478,11 @@ int serialize_state(ce_core* c, std::vector<uint8_t>* out, bool head_only = fals
     for (uint32_t s : slots)
       if (c->nov[s]) { w.bin(c->slot_actor[s].data(), 16); w.uint(c->nov[s]); }
     w.str("state");
+    if (lww) {  // { val, marker }: two integers, written here
+      write_lww_state(c, &w);
+      out->swap(w.b);
+      return CE_OK;
+    }
     if (head_only) {  // the device writer continues from here
       out->swap(w.b);
       return CE_OK;
@@ -754,6 +764,8 @@ int ingest_ops_dev_once(ce_core* c, const uint8_t* d_blob, const uint64_t* d_off
     return ds_ingest_ops(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, status_out);
   if (c->kind == CE_STATE_GSET)
     return gs_ingest_ops(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, status_out);
+  if (c->kind == CE_STATE_LWWREG)
+    return lw_ingest_ops(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, status_out);
   hipError_t e;
   const KeyRef key = key_of(c);
   const bool pnc = c->kind == CE_STATE_PNCOUNTER;
@@ -1369,7 +1381,8 @@ int ingest_states_dev(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs,
   // host pass: StateWrapper msgpack -> dots (north star: "host pass that flattens decoded
   // ops/states into columnar arrays")
   std::vector<Dots> novs(n), sts(n), negs(n);  // negs: PNCounter's n plane
-  std::vector<uint64_t> members;               // GSet: every file's `value`, one column
+  std::vector<uint64_t> members;               // GSet: every file's `value`, one column; LWWReg:
+                                               // every file's (val, marker), in file order
   int first = CE_OK;
   for (uint32_t i = 0; i < n; i++) {
     if (st[i] == CE_OK) {
@@ -1394,7 +1407,8 @@ int ingest_states_dev(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs,
     all.insert(all.end(), sts[i].begin(), sts[i].end());
     alln.insert(alln.end(), negs[i].begin(), negs[i].end());
   }
-  if ((rc = c->kind == CE_STATE_GSET ? gs_insert_members(c, members) : merge_dots_host(c, all, &alln))) return rc;
+  if (c->kind == CE_STATE_LWWREG) lw_apply_pairs(c, members);
+  else if ((rc = c->kind == CE_STATE_GSET ? gs_insert_members(c, members) : merge_dots_host(c, all, &alln))) return rc;
   for (uint32_t i = 0; i < n; i++)
     for (auto& d : novs[i]) {
       uint32_t s;
@@ -1601,7 +1615,8 @@ int compact_bytes(ce_core* c, const uint8_t* nonce, std::vector<uint8_t>* file) 
     return gs_compact_device(c, std::move(head), ingest_fmt ? kCoreVersion : c->current_data_version.data(),
                              nonce, key_of(c), file);
   }
-  if (!is_dotset_kind(c->kind) && !c->host_compact) return compact_device(c, nonce, file);
+  // (an LWWReg's state is serialized on the host, below: next_op_versions and two integers)
+  if (!is_dotset_kind(c->kind) && c->kind != CE_STATE_LWWREG && !c->host_compact) return compact_device(c, nonce, file);
   if (c->kind == CE_STATE_ORSWOT && !c->host_compact) {
     // entries serialized, sealed and downloaded once on the device (ce_dotset_io.hip)
     const bool ingest_fmt = (c->flags & CE_COMPACT_INGEST_FORMAT) != 0;
@@ -1628,7 +1643,8 @@ int ce_core_open(ce_ctx* ctx, const ce_open_options* o, ce_core** out) {
   if (!ctx || !o || !out || !o->current_data_version || (o->n_supported && !o->supported_data_versions))
     return CE_ERR_INVALID_ARG;
   if (o->state_kind != CE_STATE_VCLOCK && o->state_kind != CE_STATE_GCOUNTER &&
-      o->state_kind != CE_STATE_PNCOUNTER && o->state_kind != CE_STATE_GSET && !is_dotset_kind(o->state_kind))
+      o->state_kind != CE_STATE_PNCOUNTER && o->state_kind != CE_STATE_GSET &&
+      o->state_kind != CE_STATE_LWWREG && !is_dotset_kind(o->state_kind))
     return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(ctx->mu);
   (void)hipSetDevice(ctx->device);
@@ -1656,6 +1672,7 @@ int ce_core_open(ce_ctx* ctx, const ce_open_options* o, ce_core** out) {
   if (rc) { delete c; return rc; }
   if (is_dotset_kind(c->kind) && (rc = ds_init(c))) { ce_core_close(c); return rc; }
   if (c->kind == CE_STATE_GSET && (rc = gs_init(c))) { ce_core_close(c); return rc; }
+  if (c->kind == CE_STATE_LWWREG && (rc = lw_init(c))) { ce_core_close(c); return rc; }
   if (o->local_path || o->remote_path) {
     if (!o->local_path || !o->remote_path || o->local_path[0] != '/' || o->remote_path[0] != '/') {
       delete c;
@@ -1717,6 +1734,7 @@ void ce_core_close(ce_core* c) {
   delete c->aux;
   ds_free(c->ds);
   gs_free(c->gs);
+  lw_free(c->lw);
   delete c;
 }
 
@@ -1823,7 +1841,8 @@ static int compact_ops_device_impl(ce_core* c, const uint8_t* d_blob, const uint
   std::vector<uint8_t>& f = c->file_buf;
   int rc;
   bool merged = false;
-  const bool spec = !is_dotset_kind(c->kind) && c->kind != CE_STATE_GSET && !c->host_compact && n > 0;
+  const bool spec = !is_dotset_kind(c->kind) && c->kind != CE_STATE_GSET && c->kind != CE_STATE_LWWREG &&
+                    !c->host_compact && n > 0;
   ce_ctx* x = aux_ctx(c);  // same stream: the compaction is ordered behind the ingest
   CompactPending pend;
   uint8_t nb[24];  // one nonce for the speculative and (if needed) the repeated compaction
@@ -2097,10 +2116,12 @@ int ce_core_apply_ops(ce_core* c, const uint8_t* ops, size_t len) {
   if (!c->has_key) return c->ctx->fail(CE_ERR_NO_KEY, "no latest key");
   Dots dots, neg;  // neg: a PNCounter's Neg ops
   std::vector<uint64_t> members;  // a GSet's ops
-  const bool ds = is_dotset_kind(c->kind), gs = c->kind == CE_STATE_GSET;
+  const bool ds = is_dotset_kind(c->kind), gs = c->kind == CE_STATE_GSET, lww = c->kind == CE_STATE_LWWREG;
   if (ds) {
     int rc = ds_check_ops(c, ops, len);
     if (rc) return rc;
+  } else if (lww) {  // (val, marker) pairs
+    if (!parse_lww_ops(ops, len, &members)) return c->ctx->fail(CE_ERR_DECODE, "ops are not a Vec<LWWReg>");
   } else if (gs) {
     if (!parse_gset_ops(ops, len, &members)) return c->ctx->fail(CE_ERR_DECODE, "ops are not a Vec<u64>");
   } else if (c->kind == CE_STATE_PNCOUNTER) {
@@ -2120,8 +2141,9 @@ int ce_core_apply_ops(ce_core* c, const uint8_t* ops, size_t len) {
   if (c->storage && (rc = storage_store_op(c->storage, c->local_actor, version, file.data(), file.size())))
     return c->ctx->fail(rc, "failed writing ops file");
   // state.apply(op) for op in ops (lib.rs:710-712)
-  if ((rc = ds ? ds_apply_local_ops(c, ops, len)
-               : gs ? gs_insert_members(c, members) : merge_dots_host(c, dots, &neg)))
+  if (lww) lw_apply_pairs(c, members);
+  else if ((rc = ds ? ds_apply_local_ops(c, ops, len)
+                    : gs ? gs_insert_members(c, members) : merge_dots_host(c, dots, &neg)))
     return rc;
   // the apply may have grown the table (new Dot actors), which moves every slot: look it up again
   s = c->slot_of.at(c->local_actor);
@@ -2141,15 +2163,17 @@ int ce_core_apply_ops_batch(ce_core* c, const uint8_t* ops, const uint64_t* offs
   ce_ctx* ctx = c->ctx;
   if (!c->has_key) return ctx->fail(CE_ERR_NO_KEY, "no latest key");
   const bool ds = is_dotset_kind(c->kind);
-  const bool gs = c->kind == CE_STATE_GSET;
+  const bool gs = c->kind == CE_STATE_GSET, lww = c->kind == CE_STATE_LWWREG;
   std::vector<Dots> dots(ds ? 0 : n), negs(ds ? 0 : n);
-  std::vector<std::vector<uint64_t>> members(gs ? n : 0);  // a GSet's ops
+  std::vector<std::vector<uint64_t>> members(gs || lww ? n : 0);  // a GSet's ops; an LWWReg's (val, marker) pairs
   for (uint32_t i = 0; i < n; i++) {
     const uint8_t* p = ops + offs[i];
     const size_t l = offs[i + 1] - offs[i];
     if (ds) {
       int rc = ds_check_ops(c, p, l);
       if (rc) return rc;
+    } else if (lww) {
+      if (!parse_lww_ops(p, l, &members[i])) return ctx->fail(CE_ERR_DECODE, "ops are not a Vec<LWWReg>");
     } else if (gs) {
       if (!parse_gset_ops(p, l, &members[i])) return ctx->fail(CE_ERR_DECODE, "ops are not a Vec<u64>");
     } else if (c->kind == CE_STATE_PNCOUNTER) {
@@ -2208,8 +2232,9 @@ int ce_core_apply_ops_batch(ce_core* c, const uint8_t* ops, const uint64_t* offs
                                              foffs[i + 1] - foffs[i])))
       return ctx->fail(rc, "failed writing ops file");
     // state.apply(op) for op in ops (lib.rs:710-712), then next_op_versions.inc (lib.rs:714-715)
-    if ((rc = ds ? ds_apply_local_ops(c, ops + offs[i], offs[i + 1] - offs[i])
-                 : gs ? gs_insert_members(c, members[i]) : merge_dots_host(c, dots[i], &negs[i])))
+    if (lww) lw_apply_pairs(c, members[i]);
+    else if ((rc = ds ? ds_apply_local_ops(c, ops + offs[i], offs[i + 1] - offs[i])
+                      : gs ? gs_insert_members(c, members[i]) : merge_dots_host(c, dots[i], &negs[i])))
       return rc;
     s = c->slot_of.at(c->local_actor);  // a growth inside the apply moved the local actor's slot
     c->nov[s] = v0 + i + 1;
@@ -2234,6 +2259,7 @@ int ce_core_reset(ce_core* c) {
   c->read_states.clear();
   if (is_dotset_kind(c->kind)) return ds_reset(c);  // (the dense state array is the VClock kinds')
   if (c->kind == CE_STATE_GSET) return gs_reset(c);
+  if (c->kind == CE_STATE_LWWREG) return lw_reset(c);
   hipError_t e = hipMemsetAsync(c->d_state.p, 0, (uint64_t)state_planes(c->kind) * c->cap * 8ull, c->ctx->stream);
   if (e) return c->ctx->hip_fail(e, "reset");
   return CE_OK;
@@ -2324,7 +2350,9 @@ int ce_core_merge_state(ce_core* c, const uint8_t* sw, size_t len) {
   if (!read_state_wrapper(sw, len, c->kind, &nov, &state, &neg, &members))
     return c->ctx->fail(CE_ERR_DECODE, "not a StateWrapper");
   // state.merge(sw.state) (lib.rs:460)
-  int rc = c->kind == CE_STATE_GSET ? gs_insert_members(c, members) : merge_dots_host(c, state, &neg);
+  int rc = CE_OK;
+  if (c->kind == CE_STATE_LWWREG) lw_apply_pairs(c, members);
+  else rc = c->kind == CE_STATE_GSET ? gs_insert_members(c, members) : merge_dots_host(c, state, &neg);
   if (rc) return rc;
   for (auto& d : nov) {                // next_op_versions.merge(..) (lib.rs:461-463)
     uint32_t s;
@@ -2416,9 +2444,10 @@ int ce_core_merge_columns_device(ce_core* c, const uint8_t* const* d_parts, cons
 // ---------------------------------------------------------------------------------------
 static bool is_set_kind(int kind) { return kind == CE_STATE_ORSWOT || kind == CE_STATE_GSET; }
 static bool has_counter(int kind) { return kind == CE_STATE_GCOUNTER || kind == CE_STATE_PNCOUNTER; }
-// `which` names a clock of the kind: 0 for every kind but GSet, 1 (the n plane) for PNCounter
+// `which` names a clock of the kind: 0 for every kind but GSet and LWWReg, 1 (the n plane) for PNCounter
 static bool has_clock(int kind, int which) {
-  return kind != CE_STATE_GSET && (which == 0 || (which == 1 && kind == CE_STATE_PNCOUNTER));
+  return kind != CE_STATE_GSET && kind != CE_STATE_LWWREG &&
+         (which == 0 || (which == 1 && kind == CE_STATE_PNCOUNTER));
 }
 
 static void fill_buf(ce_buf* out, const void* p, size_t n) {
@@ -2604,6 +2633,14 @@ int ce_core_mvreg_read(ce_core* c, ce_buf* out) {
   int rc = ds_mvreg_read(c, &v);
   if (rc) return rc;
   fill_buf(out, v.data(), v.size() * 8);
+  return CE_OK;
+}
+
+int ce_core_lwwreg_read(ce_core* c, uint64_t* val, uint64_t* marker) {
+  if (!c || !val || !marker) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  if (c->kind != CE_STATE_LWWREG) return c->ctx->fail(CE_ERR_INVALID_ARG, "lwwreg_read: not an LWWReg");
+  lw_read(c, val, marker);  // (the register is committed on the host: nothing is in flight)
   return CE_OK;
 }
 

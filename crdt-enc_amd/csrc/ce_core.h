@@ -35,12 +35,14 @@ struct DsState;  // Orswot / MVReg state (ce_dotset_host.cpp)
 void ds_free(DsState* d);
 struct GsState;  // GSet<u64> state: the device hash set (ce_gset_host.cpp)
 void gs_free(GsState* g);
+struct LwState;  // LWWReg<u64, u64> state: the register and the ingest's record column (ce_lww_host.cpp)
+void lw_free(LwState* l);
 
 inline bool is_dotset_kind(int kind) { return kind == CE_STATE_ORSWOT || kind == CE_STATE_MVREG; }
 // kinds without the dense multi-GPU exchange (export / import / sharded ingest / pending batch):
 // their ranks exchange state bytes instead
 inline bool no_dense_exchange(int kind) {
-  return is_dotset_kind(kind) || kind == CE_STATE_PNCOUNTER || kind == CE_STATE_GSET;
+  return is_dotset_kind(kind) || kind == CE_STATE_PNCOUNTER || kind == CE_STATE_GSET || kind == CE_STATE_LWWREG;
 }
 // planes of the dense state and batch (u64[planes * cap]): PNCounter keeps p at [slot] and n at
 // [slot + cap]; next_op_versions is one plane for every kind
@@ -124,6 +126,7 @@ struct ce_core {
   ce_ctx* aux = nullptr;              // single-file work during a batch (exotic envelopes)
   ce::DsState* ds = nullptr;          // Orswot / MVReg state (dot-set kinds only)
   ce::GsState* gs = nullptr;          // GSet state (CE_STATE_GSET only)
+  ce::LwState* lw = nullptr;          // LWWReg state (CE_STATE_LWWREG only)
   // sharded ingest (ce_core_ingest_ops_device_sharded): the batch is folded into d_batch and
   // held there with its next_op_versions until ce_core_pending_commit
   bool pending = false;
@@ -322,5 +325,21 @@ bool parse_gset_ops(const uint8_t* p, size_t n, std::vector<uint64_t>* out);
 // GSet { value: BTreeSet<u64> }: the reader (any order, duplicates) and the canonical writer
 bool read_gset_state(Rd& r, std::vector<uint64_t>* out);
 void write_gset_state(Wr* w, const std::vector<uint64_t>& sorted_members);
+
+// LWWReg<u64, u64> (ce_lww_host.cpp): the register lives on the host; next_op_versions, the actor
+// table and the storage plumbing are ce_core.cpp's, as for every kind
+int lw_init(ce_core* c);
+int lw_reset(ce_core* c);
+int lw_ingest_ops(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n,
+                  uint64_t blob_len, const uint8_t* actors, uint32_t m, const uint32_t* d_fa,
+                  const uint64_t* d_fv, int32_t* status_out);
+// (val, marker) pairs (state files in call order, a local Vec<LWWReg>) through LWWReg::update
+void lw_apply_pairs(ce_core* c, const std::vector<uint64_t>& pairs);
+void lw_read(ce_core* c, uint64_t* val, uint64_t* marker);
+// Vec<LWWReg> as rmp-serde reads it, as (val, marker) pairs appended to out; false: CE_ERR_DECODE
+bool parse_lww_ops(const uint8_t* p, size_t n, std::vector<uint64_t>* out);
+// LWWReg { val, marker }: the reader (one pair appended) and the canonical writer
+bool read_lww_state(Rd& r, std::vector<uint64_t>* out);
+void write_lww_state(ce_core* c, Wr* w);
 
 }  // namespace ce

@@ -21,6 +21,7 @@
 
 #include "ce_device.h"
 #include "ce_gset_device.h"
+#include "ce_lww.h"
 
 namespace ce {
 
@@ -1624,6 +1625,128 @@ __device__ __forceinline__ void decode_gset_lds(const DecodeArgs& a, const SupVe
   }
 }
 
+// ---- LWWReg<u64, u64> op files decoded in the open (k_open_fold_v3's LW form) ----------------
+// The fourth grammar: the body is a Vec<LWWReg> (ce_lww.h has the element grammar and the fold's
+// order), decoded from the file's plaintext in LDS by its 16 lanes.  Nothing is folded: the group
+// leaves the file's own winner -- largest marker, lowest element index -- as one 16-byte record at
+// a.lw->rec[f] (zeroed by the host: a gated-out, failing or all-marker-0 file writes nothing), and
+// k_lww_reduce picks the batch's.  Rows are indexed by f, so the order in which the waves draw
+// their groups cannot reach the result.  As in the GSet form every byte used lies below the
+// file's own length.
+struct LwCounts {  // files by path, per lane (sub == 0 counts its group's), flushed once per wave
+  uint32_t uni = 0, gen = 0;
+  __device__ __forceinline__ void flush(const DecodeArgs& a) const {
+    uint32_t u = uni, g = gen;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      u += (uint32_t)__shfl_xor((int)u, d);
+      g += (uint32_t)__shfl_xor((int)g, d);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      if (u) atomicAdd(&a.lw->paths[0], u);
+      if (g) atomicAdd(&a.lw->paths[1], g);
+      if (u + g) atomicAdd(&a.lw->paths[2], u + g);
+    }
+  }
+};
+
+__device__ __forceinline__ unsigned long long lw_shfl_xor64(unsigned long long v, int d) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d);
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+template <int LPF, typename Pf>
+__device__ __forceinline__ void decode_lww_lds(const DecodeArgs& a, const SupVers& sup, const uint8_t* fl,
+                                               uint32_t len, bool live, bool apply, uint32_t f,
+                                               uint32_t grp, uint32_t sub, LwCounts& C, Pf&& prefetch) {
+  static_assert(LPF == 16, "the group reduce below is four xor steps");
+  int32_t st = CE_OK;
+  if (live) {
+    if (len < 16) st = CE_ERR_PT_LEN;
+    else if (!sup.has(a, *reinterpret_cast<const uint4*>(fl))) st = CE_ERR_PT_VERSION;
+  }
+  const uint8_t* body = fl + 16;
+  const uint32_t* L = reinterpret_cast<const uint32_t*>(body);
+  const uint32_t blen = len >= 16 ? len - 16 : 0;
+  uint32_t cnt = 0, h = 0;
+  if (live && st == CE_OK) {
+    if (blen == 0) st = CE_ERR_DECODE;
+    else {
+      const uint32_t m = body[0];
+      if ((m & 0xf0) == 0x90) { cnt = m & 15; h = 1; }
+      else if (m == 0xdc && blen >= 3) { cnt = (uint32_t)body[1] << 8 | body[2]; h = 3; }
+      else if (m == 0xdd && blen >= 5) {
+        cnt = (uint32_t)body[1] << 24 | (uint32_t)body[2] << 16 | (uint32_t)body[3] << 8 | body[4];
+        h = 5;
+      } else st = CE_ERR_DECODE;
+      if (st == CE_OK && cnt > blen - h) st = CE_ERR_DECODE;  // each element takes >= 1 byte
+    }
+  }
+  prefetch();
+  const bool dec = live && st == CE_OK;
+  // uniform stride: the first element's two integer markers give (wv, wm); count x stride fits,
+  // so each of a lane's elements (sub, sub + 16, ...) lies whole inside the file -- the 5-byte
+  // head, both integers and the 7-byte key -- before its windows are read.  The lane checks each
+  // of them byte for byte and keeps its best (marker, index), replacing on strictly greater only:
+  // its elements come in ascending order, so an equal marker keeps the earlier one.
+  uint32_t wv = 0, wm = 0, stride = 0;
+  if (dec && cnt > 0 && blen - h >= 14) {
+    wv = lww_uint_width((uint8_t)body[h + 5]);
+    if (wv && h + 12 + wv < blen) wm = lww_uint_width((uint8_t)body[h + 12 + wv]);
+    if (wv && wm) stride = 12 + wv + wm;
+    if (stride && (unsigned long long)cnt * stride > blen - h) stride = 0;
+  }
+  bool bad = dec && cnt > 0 && stride == 0;
+  unsigned long long bm = 0, bv = 0;
+  uint32_t bi = 0xffffffffu;
+  if (stride)
+    for (uint32_t e = sub; e < cnt && !bad; e += LPF) {
+      const uint32_t x = h + e * stride;  // (< blen <= 4080)
+      const LdsWin<4> V(L, x);            // 82 a3"val" <uint>: bytes 0 .. 5 + wv
+      uint32_t lv = 0, lm = 0;
+      const unsigned long long v = V.uint_at(5, &lv);
+      const LdsWin<4> M(L, x + 5 + wv);   // a6"marker" <uint>: bytes 0 .. 7 + wm
+      const unsigned long long m = M.uint_at(7, &lm);
+      bad = V.w[0] != 0x6176a382u || V.byte(4) != 0x6cu || lv != wv || M.w[0] != 0x72616da6u ||
+            (M.w[1] & 0xffffffu) != 0x72656bu || lm != wm;
+      if (!bad && m > bm) { bm = m; bv = v; bi = e; }
+    }
+  const bool general = dec && grp_bits<LPF>(bad, grp) != 0;
+  if (dec && sub == 0) {
+    C.uni += general ? 0u : 1u;
+    C.gen += general ? 1u : 0u;
+  }
+  // the group's best into each of its lanes: largest marker, then lowest element index
+#pragma unroll
+  for (int d = LPF / 2; d >= 1; d >>= 1) {
+    const unsigned long long om = lw_shfl_xor64(bm, d), ov = lw_shfl_xor64(bv, d);
+    const uint32_t oi = (uint32_t)__shfl_xor((int)bi, d);
+    const bool take = om > bm || (om == bm && oi < bi);
+    bm = take ? om : bm;
+    bv = take ? ov : bv;
+    bi = take ? oi : bi;
+  }
+  // general (mixed widths, the array form, another key order, unknown keys, other integer forms):
+  // the group's lane 0 walks the elements front to back through the host's parser
+  if (general && sub == 0) {
+    bm = 0;
+    bv = 0;
+    Rd q{body, blen, h};
+    for (uint32_t e = 0; e < cnt; e++) {
+      uint64_t v = 0, m = 0;
+      if (parse_lww_op(q, &v, &m) != 1) { st = CE_ERR_DECODE; break; }  // (too deep: rejected)
+      if (m > bm) { bm = m; bv = v; }
+    }
+  }
+  if (dec && st == CE_OK && apply && sub == 0 && bm != 0) a.lw->rec[f] = LwwRec{bm, bv};
+  if (live && st != CE_OK && sub == 0) {
+    a.status[f] = st;
+    atomicAdd(&a.counters[3], 1u);
+    atomicMin(&a.counters[5], f);
+  }
+}
+
 __device__ const uint32_t kPolyOne[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 
 // ----------------------------------------------------------------------------------------
@@ -1651,7 +1774,9 @@ __device__ const uint32_t kPolyOne[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
 // GS: the GSet grammar (decode_gset_lds, into the hash tables of a.gs) in place of decode_fold;
 // only k_open_fold_v3<false, true, false, true> is built.  Every GS difference is an `if
 // constexpr`: the other instantiations compile the code they always did.
-template <bool PAIR, bool EARLY, bool PN = false, bool GS = false>
+// LW: the LWWReg grammar (decode_lww_lds, one record per file into the column of a.lw), built the
+// same way; only k_open_fold_v3<false, true, false, false, true> is.
+template <bool PAIR, bool EARLY, bool PN = false, bool GS = false, bool LW = false>
 __global__ __launch_bounds__(64, 2)
 void k_open_fold_v3(DecodeArgs a) {
   constexpr int LPF = 16, F = 4, BPL = 4;
@@ -1702,6 +1827,7 @@ void k_open_fold_v3(DecodeArgs a) {
   const SupVers sup(a);
   DecState S{PN ? 51u : 38u, 0, 0, 0, 0, 0xffffffffu};
   GsCounts gsc;
+  LwCounts lwc;
   AuthFails fails;
   // this lane's tree weight r^(4q), q = (sub + 15) & 15: X = r^(4 (q & 3)) in {1, r^4, r^8,
   // r^12}, Y = r^(16 (q >> 2)) in {1, r^16, r^32, r^48}, read from FileParams.rpow / PolyAux
@@ -1889,7 +2015,11 @@ void k_open_fold_v3(DecodeArgs a) {
     // 4) data-version check, decode from LDS, fold; the next iteration's parameters are loaded
     //    inside (their latency hides under the decode)
     if (CE_V3_PRIO) __builtin_amdgcn_s_setprio(CE_V3_PRIO);  // the decode's short dependent chains first
-    if constexpr (GS) {
+    if constexpr (LW) {
+      decode_lww_lds<LPF>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, lwc, [&] {
+        if (!EARLY) nx = load_pre2(a, gn * F + grp);
+      });
+    } else if constexpr (GS) {
       decode_gset_lds<LPF>(a, sup, fl, len, act && ok, cur.apply != 0, f, grp, sub, gsc, [&] {
         if (!EARLY) nx = load_pre2(a, gn * F + grp);
       });
@@ -1901,7 +2031,8 @@ void k_open_fold_v3(DecodeArgs a) {
     if (CE_V3_PRIO) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_wave_barrier();
   }
-  if constexpr (GS) gsc.flush(a);
+  if constexpr (LW) lwc.flush(a);
+  else if constexpr (GS) gsc.flush(a);
   else flush_pending<LPF>(a, sub, S.pslot, S.pbest);
   fails.flush(a);
   if (a.stamps) {
@@ -2194,6 +2325,18 @@ hipError_t launch_open_fold_gset(hipStream_t s, const DecodeArgs& a, OpenLaunchL
   const DecodeArgs b = log.stamped(a, grid.x);
   if (t0) hipExtLaunchKernelGGL((k_open_fold_v3<false, true, false, true>), grid, dim3(64), 0, s, t0, t1, 0u, b);
   else hipLaunchKernelGGL((k_open_fold_v3<false, true, false, true>), grid, dim3(64), 0, s, b);
+  return hipGetLastError();
+}
+
+hipError_t launch_open_fold_lww(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log, hipEvent_t t0,
+                                hipEvent_t t1) {
+  if (a.n == 0) return hipSuccess;
+  if (!a.aux || !a.lw) return hipErrorInvalidValue;  // the setup's PolyAux rows, the record column
+  static const uint32_t res = resident_blocks(k_open_fold_v3<false, true, false, false, true>, 64);
+  const dim3 grid(log.grid(std::min<uint32_t>((a.n + 3) / 4, res), "open_v3_lww"));
+  const DecodeArgs b = log.stamped(a, grid.x);
+  if (t0) hipExtLaunchKernelGGL((k_open_fold_v3<false, true, false, false, true>), grid, dim3(64), 0, s, t0, t1, 0u, b);
+  else hipLaunchKernelGGL((k_open_fold_v3<false, true, false, false, true>), grid, dim3(64), 0, s, b);
   return hipGetLastError();
 }
 

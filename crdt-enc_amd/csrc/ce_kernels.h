@@ -154,6 +154,8 @@ struct DecodeArgs {
     const struct GsFused* gs;   // the fused open's GSet form (no actors in its ops): the hash tables
                                 // (ce_gset.h), device memory.  Shares the word so that the
                                 // argument block, and with it every other kernel's code, stays as it was
+    const struct LwwFused* lw;  // the fused open's LWWReg form (no actors either): the per-file
+                                // record column and the path counters (ce_lww.h), device memory
   };
   uint32_t miss_cap;
   uint8_t* refold;              // per file: had a miss
@@ -261,6 +263,10 @@ hipError_t launch_open_fold_pn(hipStream_t s, const DecodeArgs& a, OpenLaunchLog
 // the GSet form (Vec<u64> decoded from LDS into the hash tables of a.gs): needs a.aux and a.gs
 hipError_t launch_open_fold_gset(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log,
                                  hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// the LWWReg form (Vec<LWWReg> decoded from LDS, one (marker, val) record per file into the column
+// of a.lw): needs a.aux and a.lw
+hipError_t launch_open_fold_lww(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log,
+                                hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 // open only: single-page files (<= kSmallMax) into a.pt at their out_off, 16 lanes per file
 // (k_open_fold_v2<..., DEC = false>); statuses and the failure counters as the segment pass sets them
 hipError_t launch_open_small_v2(hipStream_t s, const DecodeArgs& a, OpenLaunchLog& log);

@@ -245,7 +245,7 @@ enum ce_state_kind {
                             CE_ERR_INVALID_ARG and touch nothing (ce_core_export_columns_device
                             as for any non-Orswot kind).  Ranks exchange
                             ce_core_state_bytes_device / ce_core_merge_state_device instead.     */
-  CE_STATE_GSET = 5      /* GSet<u64> {value: BTreeSet<u64>}: op = a member (an op file is a
+  CE_STATE_GSET = 5,     /* GSet<u64> {value: BTreeSet<u64>}: op = a member (an op file is a
                             Vec<u64>, any non-negative msgpack integer form).  The members live in
                             a device hash set (CE_GSET_CAP=<slots>: its starting capacity, read
                             at ce_core_open); a rejected batch leaves the set and
@@ -263,6 +263,29 @@ enum ce_state_kind {
                             CE_HOST_STATES=1: every state file, uncounted),
                             gset_state_bytes_device (ce_core_state_bytes_device calls whose
                             bytes never left HBM).                                              */
+  CE_STATE_LWWREG = 6    /* LWWReg<u64, u64> {val, marker}: op = LWWReg (an op file is a
+                            Vec<LWWReg>), apply(op) = merge(op) = update(val, marker), taken
+                            when the register's marker is strictly smaller.  An op or a state
+                            whose marker equals the register's changes nothing, and a marker 0
+                            never replaces the default (0, 0).  Among a batch's applied ops with
+                            the largest marker the first in apply order wins: the lowest file
+                            index in the call, then the lowest index in its file (the reference
+                            keeps the batch's order, lib.rs:512-541).  State files are merged in
+                            the call's file order; the reference merges them in completion order
+                            (buffer_unordered, lib.rs:452) and so leaves a tie between two state
+                            files unspecified.  A rejected batch leaves the register and
+                            next_op_versions as they were.  Entry points and the multi-GPU
+                            answers as for CE_STATE_PNCOUNTER: ranks exchange state bytes -- an
+                            address partition of the op files would break the apply order that
+                            ties depend on, so this kind has no sharded ingest.  The state is two
+                            integers: state files, ce_core_merge_state[_device] and the writer
+                            run on the host.  ce_core_lwwreg_read reads it.
+                            ce_core_path_count keys: open_v3_lww (fused open launches),
+                            lww_fused_files (decoded inside the fused open), lww_uniform_files,
+                            lww_general_files, lww_page_files (decoded from HBM by k_decode_lww:
+                            multi-page files, host-parse envelopes, multi-key retries), and two
+                            constants of the build, lww_reduce_tile and lww_reduce_max_blocks
+                            (k_lww_reduce: records per tile, and the most blocks it launches). */
 };
 
 enum ce_open_flags {
@@ -594,6 +617,9 @@ int ce_core_orswot_member_clocks(ce_core *c, const uint64_t *members, uint32_t n
 /* lib.rs:325-330 with MVReg::read().val: k u64 LE values, in the order ce_core_state_bytes writes
  * `vals`.  MVReg only.  ce_buf_free. */
 int ce_core_mvreg_read(ce_core *c, ce_buf *out);
+/* lib.rs:325-330 with |s| (s.val, s.marker): the committed register.  LWWReg only: any other kind
+ * returns CE_ERR_INVALID_ARG and touches no output. */
+int ce_core_lwwreg_read(ce_core *c, uint64_t *val, uint64_t *marker);
 
 /* Diagnostics: how many times a code path ran on this core ("states_device_read",
  * "states_host_parse", "compact_device_writer"; per multi-segment op file "segdec_records"
