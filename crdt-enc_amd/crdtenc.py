@@ -69,6 +69,9 @@ EXPORTS = [
     "ce_core_mvreg_read", "ce_core_lwwreg_read",
     "ce_ctx_prim_excl_sum_u32", "ce_ctx_prim_excl_max_by_key", "ce_ctx_prim_sort_pairs_u32",
     "ce_ctx_prim_sort_pairs_u64",
+    "ce_core_pn_ingest_ops_device_sharded", "ce_core_pn_pending_export", "ce_core_pn_pending_commit",
+    "ce_core_lwwreg_ingest_ops_device_sharded", "ce_core_lwwreg_pending_record", "ce_core_lwwreg_pending_commit",
+    "ce_ctx_prim_lww_reduce_keyed",
 ]
 
 
@@ -448,6 +451,16 @@ class Context:
         self.check(lib().ce_ctx_prim_excl_max_by_key(self.p, ctypes.c_void_p(keys_ptr), ctypes.c_void_p(vals_ptr),
                                                      ctypes.c_void_p(out_ptr), ctypes.c_uint32(n)),
                    "prim_excl_max_by_key")
+
+    def prim_lww_reduce_keyed(self, rec_ptr, fa_ptr, fv_ptr, n):
+        """(marker, val, fa, fv) of the best of n records {marker, val} (device u64[2n]) with the
+        addresses fa (u32[n]) / fv (u64[n]): largest marker, then lowest fa, fv, index; (0, 0,
+        2^64 - 1, 2^64 - 1) when every marker is 0."""
+        out = (ctypes.c_uint64 * 4)()
+        self.check(lib().ce_ctx_prim_lww_reduce_keyed(self.p, ctypes.c_void_p(rec_ptr), ctypes.c_void_p(fa_ptr),
+                                                      ctypes.c_void_p(fv_ptr), ctypes.c_uint32(n), out),
+                   "prim_lww_reduce_keyed")
+        return tuple(out)
 
     def _prim_sort(self, f, what, kin_ptr, kout_ptr, vin_ptr, vout_ptr, n, bits):
         self.check(f(self.p, ctypes.c_void_p(kin_ptr), ctypes.c_void_p(kout_ptr), ctypes.c_void_p(vin_ptr),
@@ -1078,6 +1091,57 @@ class Core:
         cs = (ctypes.c_uint64 * max(k, 1))(*counts)
         return lib().ce_core_gset_pending_commit(self.p, 1 if accept else 0, ptrs if k else None,
                                                  cs if k else None, ctypes.c_uint32(k))
+
+    # ---- CE_STATE_PNCOUNTER partitioned by op-file address (shard.ingest_sharded over a
+    # shard.DevicePnShardOps): the dense calls' contracts over both planes ----
+    def pn_ingest_ops_device_sharded(self, d_blob, d_offs, n, blob_len, actors, d_fa, d_fv, d_hi,
+                                     want_status=False):
+        st = (ctypes.c_int32 * max(n, 1))() if want_status else None
+        rc = lib().ce_core_pn_ingest_ops_device_sharded(
+            self.p, ctypes.c_void_p(d_blob), ctypes.c_void_p(d_offs), ctypes.c_uint32(n),
+            ctypes.c_uint64(blob_len), _ptr(actors)[0], ctypes.c_uint32(len(actors) // 16),
+            ctypes.c_void_p(d_fa), ctypes.c_void_p(d_fv), ctypes.c_void_p(d_hi), st)
+        return (rc, list(st)[:n]) if want_status else rc
+
+    def pn_pending_export(self, d_batch, cap_words):
+        """The pending batch (p at [slot], n at [slot + capacity]) into d_batch (u64[cap_words]);
+        False (nothing written) when it names an unregistered actor or cap_words < 2 * capacity."""
+        ready = ctypes.c_int(0)
+        self.ctx.check(lib().ce_core_pn_pending_export(self.p, ctypes.c_void_p(d_batch), ctypes.c_uint64(cap_words),
+                                                       ctypes.byref(ready)), "pn_pending_export")
+        return ready.value == 1
+
+    def pn_pending_commit(self, accept, d_import=None, import_words=0):
+        self.ctx.check(lib().ce_core_pn_pending_commit(self.p, 1 if accept else 0,
+                                                       ctypes.c_void_p(d_import) if d_import else None,
+                                                       ctypes.c_uint64(import_words)),
+                       "pn_pending_commit")
+
+    # ---- CE_STATE_LWWREG partitioned by op-file address (shard.ingest_lwwreg_sharded) ----
+    def lwwreg_ingest_ops_device_sharded(self, d_blob, d_offs, n, blob_len, actors, d_fa, d_fv, d_hi,
+                                         want_status=False):
+        st = (ctypes.c_int32 * max(n, 1))() if want_status else None
+        rc = lib().ce_core_lwwreg_ingest_ops_device_sharded(
+            self.p, ctypes.c_void_p(d_blob), ctypes.c_void_p(d_offs), ctypes.c_uint32(n),
+            ctypes.c_uint64(blob_len), _ptr(actors)[0], ctypes.c_uint32(len(actors) // 16),
+            ctypes.c_void_p(d_fa), ctypes.c_void_p(d_fv), ctypes.c_void_p(d_hi), st)
+        return (rc, list(st)[:n]) if want_status else rc
+
+    def lwwreg_pending_record(self):
+        """(rc, (marker, val, writer index, version)) of the pending winner; (0, 0, 2^64 - 1,
+        2^64 - 1) for none; rc INVALID_ARG and None when nothing is pending."""
+        rec = (ctypes.c_uint64 * 4)()
+        rc = lib().ce_core_lwwreg_pending_record(self.p, rec)
+        return rc, (None if rc else tuple(rec))
+
+    def lwwreg_pending_commit(self, accept, recs=()):
+        """accept: the register takes the best of the local pending winner and the remote records
+        (4-tuples as lwwreg_pending_record gives them, at most 64); else the pending batch is
+        dropped.  Returns the status."""
+        k = len(recs)
+        flat = (ctypes.c_uint64 * max(4 * k, 1))(*[int(x) & 0xFFFFFFFFFFFFFFFF for r in recs for x in r])
+        return lib().ce_core_lwwreg_pending_commit(self.p, 1 if accept else 0, flat if k else None,
+                                                   ctypes.c_uint32(k))
 
     # ---- with_state reads (lib.rs:325-330): the committed state answered from HBM ----
     def contains_device(self, d_members, n, d_out):

@@ -2260,6 +2260,9 @@ int ce_core_reset(ce_core* c) {
   if (is_dotset_kind(c->kind)) return ds_reset(c);  // (the dense state array is the VClock kinds')
   if (c->kind == CE_STATE_GSET) return gs_reset(c);
   if (c->kind == CE_STATE_LWWREG) return lw_reset(c);
+  // a batch left pending by ce_core_pn_ingest_ops_device_sharded goes with the state (the GSet
+  // rule; a VClock / GCounter batch stays pending across a reset, as it always has)
+  if (c->kind == CE_STATE_PNCOUNTER) c->pending = false;
   hipError_t e = hipMemsetAsync(c->d_state.p, 0, (uint64_t)state_planes(c->kind) * c->cap * 8ull, c->ctx->stream);
   if (e) return c->ctx->hip_fail(e, "reset");
   return CE_OK;

@@ -39,8 +39,9 @@ struct LwState;  // LWWReg<u64, u64> state: the register and the ingest's record
 void lw_free(LwState* l);
 
 inline bool is_dotset_kind(int kind) { return kind == CE_STATE_ORSWOT || kind == CE_STATE_MVREG; }
-// kinds without the dense multi-GPU exchange (export / import / sharded ingest / pending batch):
-// their ranks exchange state bytes instead
+// kinds the dense multi-GPU calls refuse (export / import / the generic sharded ingest and pending
+// batch): whole states travel as state bytes, and GSet, PNCounter and LWWReg have sharded-ingest
+// entry points of their own (ce_core_gset_*, ce_core_pn_*, ce_core_lwwreg_*)
 inline bool no_dense_exchange(int kind) {
   return is_dotset_kind(kind) || kind == CE_STATE_PNCOUNTER || kind == CE_STATE_GSET || kind == CE_STATE_LWWREG;
 }
@@ -246,6 +247,19 @@ int merge_dots_host(ce_core* c, const Dots& dots, const Dots* neg = nullptr);
 int ingest_ops_dev_sharded(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n,
                            uint64_t blob_len, const uint8_t* actors, uint32_t m, const uint32_t* d_fa,
                            const uint64_t* d_fv, const uint64_t* shard_hi, int32_t* status_out);
+
+// Shared by the kinds' own sharded ingests (ce_shard_host.cpp).
+// next_op_versions.get(writer) of m writers (16 bytes each), 0 for one without a slot
+void writer_versions_of(const ce_core* c, const uint8_t* actors, uint32_t m, std::vector<uint64_t>* e0);
+// The sharded gate on the device: apply[i] = expect[writer] <= version < d_hi[writer]
+// (k_gate_window over the windows every rank agreed on, into ctx->apply).  gate: the caller's
+// scratch for e0 u64[m] | newnov u64[m].  The host reads back the m window ends and the flags
+// word, no per-file metadata: expect[a] = max(expect[a], hi[a]), *gap = the windows stop at a gap.
+// CE_ERR_SHARD (flags kShardBad / kShardE0Mismatch): nothing may be opened or folded.
+int shard_gate_window(ce_core* c, DevBuf* gate, uint32_t n, uint32_t m, const uint32_t* d_fa,
+                      const uint64_t* d_fv, const uint64_t* d_hi, std::vector<uint64_t>* expect, bool* gap);
+// a pending batch's next_op_versions (c->pending_nov, lib.rs:537-538) into the table, uploaded
+int commit_pending_nov(ce_core* c);
 
 // dot-set kinds (ce_dotset_host.cpp): same contracts as the VClock/GCounter paths in ce_core.cpp
 int ds_init(ce_core* c);

@@ -11,6 +11,7 @@
 #include "ce_dotset.h"
 #include "ce_dotset_io.h"
 #include "ce_internal.h"
+#include "ce_lww.h"
 
 namespace ce {
 
@@ -504,6 +505,27 @@ int ce_ctx_prim_sort_pairs_u64(ce_ctx* c, const uint64_t* d_kin, uint64_t* d_kou
   return prim_run(c, "prim sort_pairs_u64", n && (!d_kin || !d_kout || !d_vin || !d_vout), [&](void* tmp, size_t& tb) {
     return sort_pairs_u64(tmp, tb, reinterpret_cast<const unsigned long long*>(d_kin),
                           reinterpret_cast<unsigned long long*>(d_kout), d_vin, d_vout, n, bits, c->stream);
+  });
+}
+
+int ce_ctx_prim_lww_reduce_keyed(ce_ctx* c, const uint64_t* d_rec, const uint32_t* d_fa, const uint64_t* d_fv,
+                                 uint32_t n, uint64_t out[4]) {
+  static_assert(sizeof(LwwKeyed) == 32 && sizeof(LwwRec) == 16, "the records of the C interface");
+  if (n == 0 && c && out) {  // nothing to reduce: "none", nothing launched
+    std::memcpy(out, &kLwwKeyedNone, sizeof(LwwKeyed));
+    return CE_OK;
+  }
+  constexpr size_t kOutAt = sizeof(LwwKeyedPartial) * kLwwMaxBlocks;
+  return prim_run(c, "prim lww_reduce_keyed", !d_rec || !d_fa || !d_fv || !out, [&](void* tmp, size_t& tb) {
+    if (!tmp) {
+      tb = kOutAt + sizeof(LwwKeyed);
+      return hipSuccess;
+    }
+    LwwKeyed* d_out = reinterpret_cast<LwwKeyed*>(static_cast<uint8_t*>(tmp) + kOutAt);
+    hipError_t e = launch_lww_reduce_keyed(c->stream, reinterpret_cast<const LwwRec*>(d_rec), d_fa, d_fv, n,
+                                           static_cast<LwwKeyedPartial*>(tmp), d_out, test_grid_cap());
+    // (prim_run waits for the stream before it frees tmp)
+    return e ? e : hipMemcpyAsync(out, d_out, sizeof(LwwKeyed), hipMemcpyDeviceToHost, c->stream);
   });
 }
 

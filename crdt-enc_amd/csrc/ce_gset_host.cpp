@@ -22,7 +22,6 @@
 #include "ce_dotset.h"
 #include "ce_dotset_io.h"
 #include "ce_gset.h"
-#include "ce_shard.h"
 
 namespace ce {
 
@@ -730,44 +729,6 @@ int gate_host(ce_core* c, uint32_t n, uint32_t m, const uint32_t* d_fa, const ui
   return CE_OK;
 }
 
-// the sharded gate on the device: apply[i] = e0 <= version < d_hi[writer] (k_gate_window over the
-// windows every rank agreed on).  The host reads back the m window ends and the flags word, no
-// per-file metadata.  CE_ERR_SHARD (flags kShardBad / kShardE0Mismatch): nothing may be folded.
-int gate_window(ce_core* c, uint32_t n, uint32_t m, const uint32_t* d_fa, const uint64_t* d_fv,
-                const uint64_t* d_hi, GsGate* gt) {
-  ce_ctx* ctx = c->ctx;
-  GsState* g = c->gs;
-  hipError_t e;
-  // gate block: e0 u64[m] | newnov u64[m]
-  if ((e = g->gate.reserve(16ull * m + 64)) || (e = ctx->counters.reserve(256)))
-    return ctx->hip_fail(e, "gate reserve");
-  uint8_t* gb = g->gate.as<uint8_t>();
-  GateArgs ga{};
-  ga.fa = d_fa;
-  ga.fv = d_fv;
-  ga.n = n;
-  ga.m = m;
-  ga.e0 = reinterpret_cast<const uint64_t*>(gb);
-  ga.newnov = reinterpret_cast<unsigned long long*>(gb + 8ull * m);
-  ga.apply = ctx->apply.as<uint8_t>();
-  std::vector<uint64_t> hi(m + 1);
-  const int t = ctx->tbegin("gate");
-  if ((m && (e = hipMemcpyAsync(gb, gt->expect.data(), 8ull * m, hipMemcpyHostToDevice, ctx->stream))) ||
-      (e = launch_gate_window(ctx->stream, ga, d_hi, ctx->counters.as<uint32_t>())))
-    return ctx->hip_fail(e, "gate");
-  ctx->tend(t);
-  if ((e = hipMemcpyAsync(hi.data(), d_hi, (m + 1) * 8ull, hipMemcpyDeviceToHost, ctx->stream)) ||
-      (e = stream_wait(ctx->stream)))
-    return ctx->hip_fail(e, "gate");
-  if (hi[m] & (kShardBad | kShardE0Mismatch))
-    return ctx->fail(CE_ERR_SHARD, hi[m] & kShardE0Mismatch
-                                       ? "ranks started from different next_op_versions"
-                                       : "a rank's batch breaks the partition contract: exact windows needed");
-  for (uint32_t a = 0; a < m; a++) gt->expect[a] = std::max(gt->expect[a], hi[a]);
-  gt->gap = (hi[m] & kShardGap) != 0;
-  return CE_OK;
-}
-
 // Every file opened, checked and decoded whatever the gate says, the gated files' members (apply[],
 // already on the device) into the batch table.  A failing file: its status is returned, the batch
 // table is cleared and the committed set untouched (all-or-nothing, lib.rs:497-514).
@@ -934,15 +895,10 @@ static int gs_ingest_ops_sharded(ce_core* c, const uint8_t* d_blob, const uint64
     hipError_t e;
     if ((c->gs->batch_dirty && (rc = clear_batch(c)))) return rc;
     if ((e = c->ctx->apply.reserve(64))) return c->ctx->hip_fail(e, "ingest reserve");
-    gt.expect.assign(m, 0);
-    for (uint32_t a = 0; a < m; a++) {
-      Uuid u;
-      std::memcpy(u.data(), actors + 16ull * a, 16);
-      auto it = c->slot_of.find(u);
-      if (it != c->slot_of.end()) gt.expect[a] = c->nov[it->second];
-    }
+    writer_versions_of(c, actors, m, &gt.expect);
   }
-  if ((rc = gate_window(c, n, m, d_fa, d_fv, d_hi, &gt))) return rc;
+  // the gate on the device (shard_gate_window): the windows every rank agreed on
+  if ((rc = shard_gate_window(c, &c->gs->gate, n, m, d_fa, d_fv, d_hi, &gt.expect, &gt.gap))) return rc;
   if (n && (rc = fold_batch(c, d_blob, d_offs, n, blob_len, status_out))) return rc;
   // pending until the commit: the windows' next_op_versions (lib.rs:537-538)
   c->pending_nov.clear();
@@ -1050,14 +1006,7 @@ int ce_core_gset_pending_commit(ce_core* c, int accept, const uint64_t* const* d
     }
     ctx->tend(t);
   }
-  if ((rc = clear_batch(c))) return rc;
-  for (auto& p : c->pending_nov) {  // next_op_versions.inc per applied file (lib.rs:537-538)
-    if (p.second == 0) continue;   // nothing applied and nothing known: no entry (VClock::get = 0)
-    uint32_t slot;
-    if ((rc = insert_actor(c, p.first, &slot))) return rc;
-    c->nov[slot] = std::max(c->nov[slot], p.second);
-  }
-  if ((rc = table_upload(c))) return rc;
+  if ((rc = clear_batch(c)) || (rc = commit_pending_nov(c))) return rc;
   // the parts are the caller's buffers: read by the time this returns
   if ((e = stream_wait(s))) return ctx->hip_fail(e, "gset commit");
   return CE_OK;

@@ -103,4 +103,32 @@ struct LwwPartial {
 hipError_t launch_lww_reduce(hipStream_t s, const LwwRec* rec, uint32_t n, LwwPartial* part, LwwRec* out,
                              uint32_t grid_cap);
 
+// k_lww_reduce_keyed: the sharded ingest's reduce (ce_core_lwwreg_ingest_ops_device_sharded).  A
+// rank holds a share of the batch, and the whole batch's apply order is (index in the shared
+// writer list, version): record i is read together with its address (fa[i], fv[i]) and the argmax
+// is by (marker descending, fa ascending, fv ascending, local index ascending) -- the keys
+// themselves, since a share's writer runs may come in any order; the local index only separates
+// two files given the same address, which Storage cannot produce.  The winner leaves with its
+// address, so the best of the ranks' winners under the same order is the whole batch's.  Same
+// tiling, grid and grid_cap as k_lww_reduce; marker 0 never wins: out = kLwwKeyedNone then.
+struct LwwKeyed {  // a share's winner (32 bytes): what the ranks exchange
+  unsigned long long marker, val, fa, fv;
+};
+static constexpr LwwKeyed kLwwKeyedNone = {0ull, 0ull, ~0ull, ~0ull};
+struct LwwKeyedPartial {
+  unsigned long long marker, val, fv;
+  uint32_t fa, idx;
+};
+// a beats b in the batch's apply order among equal markers, and by marker first
+CE_HD bool lww_keyed_better(unsigned long long ma, unsigned long long faa, unsigned long long fva, uint32_t ia,
+                            unsigned long long mb, unsigned long long fab, unsigned long long fvb, uint32_t ib) {
+  if (ma != mb) return ma > mb;
+  if (faa != fab) return faa < fab;
+  if (fva != fvb) return fva < fvb;
+  return ia < ib;
+}
+// part: kLwwMaxBlocks partials of scratch; out: one record.  n >= 1
+hipError_t launch_lww_reduce_keyed(hipStream_t s, const LwwRec* rec, const uint32_t* fa, const uint64_t* fv,
+                                   uint32_t n, LwwKeyedPartial* part, LwwKeyed* out, uint32_t grid_cap);
+
 }  // namespace ce

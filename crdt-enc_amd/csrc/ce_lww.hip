@@ -1,6 +1,7 @@
 // ce_lww.hip -- LWWReg<u64, u64> on the device (gfx950): the wave-per-file decode of an op file's
 // Vec<LWWReg> from plaintext in HBM (multi-page files, host-parse envelopes, multi-key retries)
-// and the reduce of the per-file records (ce_lww.h) to the batch's winner.
+// and the reduce of the per-file records (ce_lww.h) to the batch's winner (k_lww_reduce by file
+// index; k_lww_reduce_keyed by the files' addresses, for a share of a batch partitioned across ranks).
 //
 // Element grammar: parse_lww_op (ce_lww.h).  The form rmp-serde's to_vec_named writes is
 //   82 a3"val" <uint> a6"marker" <uint>      12 + wv + wm bytes, wv, wm in {1, 2, 3, 5, 9}
@@ -197,6 +198,79 @@ __global__ __launch_bounds__(kLwwBlock) void k_lww_reduce_final(const LwwPartial
   if (threadIdx.x == 0) out[0] = LwwRec{bm, bm ? bv : 0ull};
 }
 
+// ---- the keyed reduce: the same two stages, each candidate carried with its address ----
+struct Keyed {
+  unsigned long long m, v, fv;
+  uint32_t fa, i;
+};
+
+__device__ __forceinline__ bool keyed_better(const Keyed& a, const Keyed& b) {
+  return lww_keyed_better(a.m, a.fa, a.fv, a.i, b.m, b.fa, b.fv, b.i);
+}
+
+// the wave's best into every lane
+__device__ __forceinline__ void wave_best_keyed(Keyed& x) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    Keyed o;
+    o.m = shfl_xor64(x.m, d);
+    o.v = shfl_xor64(x.v, d);
+    o.fv = shfl_xor64(x.fv, d);
+    o.fa = (uint32_t)__shfl_xor((int)x.fa, d);
+    o.i = (uint32_t)__shfl_xor((int)x.i, d);
+    if (keyed_better(o, x)) x = o;
+  }
+}
+
+// the block's best into thread 0
+__device__ __forceinline__ void block_best_keyed(Keyed& x) {
+  __shared__ Keyed s_k[kLwwBlock / 64];
+  wave_best_keyed(x);
+  const uint32_t w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) s_k[w] = x;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (uint32_t k = 1; k < kLwwBlock / 64; k++)
+      if (keyed_better(s_k[k], x)) x = s_k[k];
+}
+
+// stage 1: as k_lww_reduce, record i read with fa[i] / fv[i]
+__global__ __launch_bounds__(kLwwBlock) void k_lww_reduce_keyed(const LwwRec* rec, const uint32_t* fa,
+                                                                const uint64_t* fv, uint32_t n,
+                                                                LwwKeyedPartial* part) {
+  Keyed b{0ull, 0ull, ~0ull, 0xffffffffu, 0xffffffffu};
+  const uint32_t tiles = (uint32_t)(((unsigned long long)n + kLwwTile - 1) / kLwwTile);
+  for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    // (t < tiles: t * kLwwTile < n; the indices below are computed in 64 bits)
+    const unsigned long long base = (unsigned long long)t * kLwwTile;
+#pragma unroll
+    for (uint32_t r = 0; r < kLwwTile / kLwwBlock; r++) {
+      const unsigned long long i = base + r * kLwwBlock + threadIdx.x;
+      if (i < n) {
+        const LwwRec x = rec[i];
+        const Keyed c{x.marker, x.val, fv[i], fa[i], (uint32_t)i};
+        if (keyed_better(c, b)) b = c;
+      }
+    }
+  }
+  block_best_keyed(b);
+  if (threadIdx.x == 0) part[blockIdx.x] = LwwKeyedPartial{b.m, b.v, b.fv, b.fa, b.i};
+}
+
+// the final stage: one block over the k <= kLwwMaxBlocks partials
+__global__ __launch_bounds__(kLwwBlock) void k_lww_reduce_keyed_final(const LwwKeyedPartial* part, uint32_t k,
+                                                                      LwwKeyed* out) {
+  Keyed b{0ull, 0ull, ~0ull, 0xffffffffu, 0xffffffffu};
+  for (uint32_t j = threadIdx.x; j < k; j += kLwwBlock) {
+    const LwwKeyedPartial p = part[j];
+    const Keyed c{p.marker, p.val, p.fv, p.fa, p.idx};
+    if (keyed_better(c, b)) b = c;
+  }
+  block_best_keyed(b);
+  if (threadIdx.x == 0)
+    out[0] = b.m ? LwwKeyed{b.m, b.v, (unsigned long long)b.fa, b.fv} : LwwKeyed{0ull, 0ull, ~0ull, ~0ull};
+}
+
 }  // namespace
 
 hipError_t launch_decode_lww(hipStream_t s, const LwwDecodeArgs& a, uint32_t grid_waves) {
@@ -214,6 +288,17 @@ hipError_t launch_lww_reduce(hipStream_t s, const LwwRec* rec, uint32_t n, LwwPa
   if (grid_cap && blocks > grid_cap) blocks = grid_cap;
   hipLaunchKernelGGL(k_lww_reduce, dim3(blocks), dim3(kLwwBlock), 0, s, rec, n, part);
   hipLaunchKernelGGL(k_lww_reduce_final, dim3(1), dim3(kLwwBlock), 0, s, part, blocks, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_lww_reduce_keyed(hipStream_t s, const LwwRec* rec, const uint32_t* fa, const uint64_t* fv,
+                                   uint32_t n, LwwKeyedPartial* part, LwwKeyed* out, uint32_t grid_cap) {
+  if (n == 0) return hipErrorInvalidValue;
+  const uint32_t tiles = (uint32_t)(((uint64_t)n + kLwwTile - 1) / kLwwTile);
+  uint32_t blocks = tiles < kLwwMaxBlocks ? tiles : kLwwMaxBlocks;
+  if (grid_cap && blocks > grid_cap) blocks = grid_cap;
+  hipLaunchKernelGGL(k_lww_reduce_keyed, dim3(blocks), dim3(kLwwBlock), 0, s, rec, fa, fv, n, part);
+  hipLaunchKernelGGL(k_lww_reduce_keyed_final, dim3(1), dim3(kLwwBlock), 0, s, part, blocks, out);
   return hipGetLastError();
 }
 

@@ -14,6 +14,12 @@
 // read_remote_ops keeps the batch's order).  State files and merge_state are parsed on the host
 // and applied in call order -- the reference merges states in completion order and so leaves a tie
 // between two of them unspecified.
+//
+// The sharded ingest (ce_core_lwwreg_ingest_ops_device_sharded, at the end of this file): a rank
+// opens and decodes its share of a batch partitioned by op-file address in the same way, gates it
+// on the device by the agreed windows, and keeps its winner PENDING with the file's (writer index,
+// version), its place in the whole batch's apply order; ce_core_lwwreg_pending_commit applies the
+// best of the ranks' winners in that order, which is the single fold's winner.
 #include <algorithm>
 #include <cstring>
 
@@ -29,6 +35,11 @@ struct LwState {
   DevBuf fused;                  // LwwFused: what the fused open reads through DecodeArgs.lw
   LwwFused h_fused;              // its host copy (lives through the upload)
   DevBuf only;
+  // the sharded ingest: the window gate's block, the keyed reduce's scratch and the share's
+  // winner, pending (with ce_core.pending / pending_nov) until ce_core_lwwreg_pending_commit
+  DevBuf gate;                   // e0 u64[m] | newnov u64[m]
+  DevBuf kred;                   // LwwKeyedPartial[kLwwMaxBlocks] | LwwKeyed (the result)
+  LwwKeyed pend = kLwwKeyedNone;
 };
 
 void lw_free(LwState* l) { delete l; }
@@ -145,9 +156,10 @@ int gate_host(ce_core* c, uint32_t n, uint32_t m, const uint32_t* d_fa, const ui
 
 // Every file opened, checked and decoded whatever the gate says; the gated files' winners
 // (apply[], already on the device) into their rows of the record column.  A failing file: its
-// status is returned and nothing else happens.  *win: the batch's winner, (0, 0) for none.
-int fold_batch(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n, uint64_t blob_len,
-               int32_t* status_out, LwwRec* win) {
+// status is returned (the lowest failing file's) and the column is not to be reduced.  Shared by
+// the unsharded and the sharded ingest.
+int open_decode(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n, uint64_t blob_len,
+                int32_t* status_out) {
   ce_ctx* ctx = c->ctx;
   LwState* l = c->lw;
   hipError_t e;
@@ -249,8 +261,20 @@ int fold_batch(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32
   if (status_out) std::memcpy(status_out, st.data(), n * 4ull);
   for (uint32_t i = 0; i < n; i++)
     if (st[i] != CE_OK) return st[i];  // all-or-nothing: the register is untouched
+  return CE_OK;
+}
+
+// open_decode, then the batch's winner by (marker descending, file index ascending); *win: (0, 0)
+// for none
+int fold_batch(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n, uint64_t blob_len,
+               int32_t* status_out, LwwRec* win) {
+  ce_ctx* ctx = c->ctx;
+  LwState* l = c->lw;
+  hipError_t e;
+  int rc;
+  if ((rc = open_decode(c, d_blob, d_offs, n, blob_len, status_out))) return rc;
   // the batch's winner: largest marker, lowest file index
-  t = ctx->tbegin("lww_reduce");
+  const int t = ctx->tbegin("lww_reduce");
   if ((e = launch_lww_reduce(ctx->stream, l->rec.as<LwwRec>(), n, l->red.as<LwwPartial>(), result_of(l),
                              test_grid_cap())))
     return ctx->hip_fail(e, "lww reduce");
@@ -302,6 +326,7 @@ int lw_init(ce_core* c) {
 
 int lw_reset(ce_core* c) {
   c->lw->val = c->lw->marker = 0;
+  c->pending = false;  // a pending sharded batch goes with the register
   return CE_OK;
 }
 
@@ -334,4 +359,106 @@ int lw_ingest_ops(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uin
   return CE_OK;
 }
 
+// The sharded ingest (crdtenc shard.ingest_lwwreg_sharded): the same open and decode with the
+// agreed windows as the gate, the share's winner left PENDING with its address (writer index in
+// the shared list, version) for ce_core_lwwreg_pending_record / _commit.
+static int lw_ingest_ops_sharded(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n,
+                                 uint64_t blob_len, const uint8_t* actors, uint32_t m, const uint32_t* d_fa,
+                                 const uint64_t* d_fv, const uint64_t* d_hi, int32_t* status_out) {
+  ce_ctx* ctx = c->ctx;
+  LwState* l = c->lw;
+  LwGate gt;
+  hipError_t e;
+  int rc;
+  bool gap = false;
+  c->pending = false;
+  if (!c->has_key) return ctx->fail(CE_ERR_NO_KEY, "no latest key");
+  if (n) {
+    if ((rc = prepare_ingest(c, n, blob_len, actors, m, &gt))) return rc;
+  } else {
+    // no file on this rank: the windows still set next_op_versions, and the pending record is
+    // "none" (no writer needs a slot before the commit)
+    if ((e = ctx->apply.reserve(64))) return ctx->hip_fail(e, "ingest reserve");
+    writer_versions_of(c, actors, m, &gt.expect);
+  }
+  if ((rc = shard_gate_window(c, &l->gate, n, m, d_fa, d_fv, d_hi, &gt.expect, &gap))) return rc;
+  LwwKeyed win = kLwwKeyedNone;
+  if (n) {
+    if ((rc = open_decode(c, d_blob, d_offs, n, blob_len, status_out))) return rc;
+    // the share's winner: largest marker, then the earliest (writer, version) of the whole batch
+    constexpr uint64_t kOutAt = sizeof(LwwKeyedPartial) * kLwwMaxBlocks;
+    if ((e = l->kred.reserve(kOutAt + sizeof(LwwKeyed)))) return ctx->hip_fail(e, "lww reduce");
+    LwwKeyed* out = reinterpret_cast<LwwKeyed*>(l->kred.as<uint8_t>() + kOutAt);
+    const int t = ctx->tbegin("lww_reduce");
+    if ((e = launch_lww_reduce_keyed(ctx->stream, l->rec.as<LwwRec>(), d_fa, d_fv, n, l->kred.as<LwwKeyedPartial>(),
+                                     out, test_grid_cap())))
+      return ctx->hip_fail(e, "lww reduce");
+    ctx->tend(t);
+    if ((e = hipMemcpyAsync(&win, out, sizeof(LwwKeyed), hipMemcpyDeviceToHost, ctx->stream)) ||
+        (e = stream_wait(ctx->stream)))
+      return ctx->hip_fail(e, "lww reduce");
+  }
+  // pending until the commit: the winner and the windows' next_op_versions (lib.rs:537-538)
+  l->pend = win;
+  c->pending_nov.clear();
+  for (uint32_t a = 0; a < m; a++) {
+    Uuid u;
+    std::memcpy(u.data(), actors + 16ull * a, 16);
+    c->pending_nov.push_back({u, gt.expect[a]});
+  }
+  c->pending = true;
+  c->pending_gen = c->table_gen;
+  return gap ? CE_ERR_OP_VERSION : CE_OK;
+}
+
 }  // namespace ce
+
+using namespace ce;
+
+extern "C" {
+
+int ce_core_lwwreg_ingest_ops_device_sharded(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n,
+                                             uint64_t blob_len, const uint8_t* actors, uint32_t m,
+                                             const uint32_t* d_fa, const uint64_t* d_fv, const uint64_t* d_hi,
+                                             int32_t* status) {
+  if (!c || (n && (!d_blob || !d_offs || !d_fa || !d_fv)) || (m && !actors) || !d_hi || c->kind != CE_STATE_LWWREG)
+    return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  return lw_ingest_ops_sharded(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, d_hi, status);
+}
+
+int ce_core_lwwreg_pending_record(ce_core* c, uint64_t rec[4]) {
+  if (!c || !rec || c->kind != CE_STATE_LWWREG) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(c->ctx->mu);
+  if (!c->pending) return c->ctx->fail(CE_ERR_INVALID_ARG, "no pending batch");
+  const LwwKeyed& w = c->lw->pend;
+  rec[0] = w.marker;
+  rec[1] = w.val;
+  rec[2] = w.fa;
+  rec[3] = w.fv;
+  return CE_OK;
+}
+
+int ce_core_lwwreg_pending_commit(ce_core* c, int accept, const uint64_t* recs, uint32_t k) {
+  if (!c || c->kind != CE_STATE_LWWREG) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  ce_ctx* ctx = c->ctx;
+  // the arguments first: a refused call leaves the batch pending
+  if (k > 64 || (k && !recs)) return ctx->fail(CE_ERR_INVALID_ARG, "at most 64 remote records");
+  if (!c->pending) return ctx->fail(CE_ERR_INVALID_ARG, "no pending batch");
+  c->pending = false;
+  if (!accept) return CE_OK;  // another rank's batch failed: the state stays unchanged
+  // the whole batch's winner: the best of the shares' winners in the batch's apply order
+  LwwKeyed best = c->lw->pend;
+  for (uint32_t i = 0; i < k; i++) {
+    const uint64_t* r = recs + 4ull * i;
+    if (r[0] && lww_keyed_better(r[0], r[2], r[3], 0, best.marker, best.fa, best.fv, 0))
+      best = LwwKeyed{r[0], r[1], r[2], r[3]};
+  }
+  if (best.marker) update(c->lw, best.val, best.marker);  // (a tie with the register keeps the incumbent)
+  return commit_pending_nov(c);
+}
+
+}  // extern "C"

@@ -13,6 +13,7 @@
 //   ce_core_shard_stats -> all_reduce(MAX) -> ce_core_shard_window -> ce_core_ingest_ops_device_
 //   sharded (folded, pending) -> pending batch all_reduce(MAX) with the failure flags ->
 //   ce_core_pending_commit on every rank (or none: all-or-nothing across ranks, lib.rs:497-514).
+// PNCounter: the same steps through ce_core_pn_*, the batch both planes (p, then n) of the array.
 #include <algorithm>
 #include <cstring>
 #include <numeric>
@@ -21,6 +22,64 @@
 #include "ce_shard.h"
 
 using namespace ce;
+
+namespace ce {
+
+void writer_versions_of(const ce_core* c, const uint8_t* actors, uint32_t m, std::vector<uint64_t>* e0) {
+  e0->assign(m, 0);
+  for (uint32_t a = 0; a < m; a++) {
+    Uuid u;
+    std::memcpy(u.data(), actors + 16ull * a, 16);
+    auto it = c->slot_of.find(u);
+    if (it != c->slot_of.end()) (*e0)[a] = c->nov[it->second];
+  }
+}
+
+int shard_gate_window(ce_core* c, DevBuf* gate, uint32_t n, uint32_t m, const uint32_t* d_fa,
+                      const uint64_t* d_fv, const uint64_t* d_hi, std::vector<uint64_t>* expect, bool* gap) {
+  ce_ctx* ctx = c->ctx;
+  hipError_t e;
+  if ((e = gate->reserve(16ull * m + 64)) || (e = ctx->counters.reserve(256)))
+    return ctx->hip_fail(e, "gate reserve");
+  uint8_t* gb = gate->as<uint8_t>();
+  GateArgs ga{};
+  ga.fa = d_fa;
+  ga.fv = d_fv;
+  ga.n = n;
+  ga.m = m;
+  ga.e0 = reinterpret_cast<const uint64_t*>(gb);
+  ga.newnov = reinterpret_cast<unsigned long long*>(gb + 8ull * m);
+  ga.apply = ctx->apply.as<uint8_t>();
+  std::vector<uint64_t> hi(m + 1);
+  const int t = ctx->tbegin("gate");
+  if ((m && (e = hipMemcpyAsync(gb, expect->data(), 8ull * m, hipMemcpyHostToDevice, ctx->stream))) ||
+      (e = launch_gate_window(ctx->stream, ga, d_hi, ctx->counters.as<uint32_t>())))
+    return ctx->hip_fail(e, "gate");
+  ctx->tend(t);
+  if ((e = hipMemcpyAsync(hi.data(), d_hi, (m + 1) * 8ull, hipMemcpyDeviceToHost, ctx->stream)) ||
+      (e = stream_wait(ctx->stream)))
+    return ctx->hip_fail(e, "gate");
+  if (hi[m] & (kShardBad | kShardE0Mismatch))
+    return ctx->fail(CE_ERR_SHARD, hi[m] & kShardE0Mismatch
+                                       ? "ranks started from different next_op_versions"
+                                       : "a rank's batch breaks the partition contract: exact windows needed");
+  for (uint32_t a = 0; a < m; a++) (*expect)[a] = std::max((*expect)[a], hi[a]);
+  *gap = (hi[m] & kShardGap) != 0;
+  return CE_OK;
+}
+
+int commit_pending_nov(ce_core* c) {
+  for (auto& p : c->pending_nov) {  // next_op_versions.inc per applied file (lib.rs:537-538)
+    if (p.second == 0) continue;   // nothing applied and nothing known: no entry (VClock::get = 0)
+    uint32_t s;
+    int rc = insert_actor(c, p.first, &s);
+    if (rc) return rc;
+    c->nov[s] = std::max(c->nov[s], p.second);
+  }
+  return table_upload(c);
+}
+
+}  // namespace ce
 
 namespace {
 
@@ -48,13 +107,7 @@ inline uint64_t dec(long long x) { return (uint64_t)x ^ kShardFlip; }
 // the writers' expected versions (next_op_versions.get, lib.rs:519) and UUID words -> device
 int stage_writers(ce_core* c, const uint8_t* actors, uint32_t m, std::vector<uint64_t>* e0) {
   ce_ctx* ctx = c->ctx;
-  e0->assign(m, 0);
-  for (uint32_t a = 0; a < m; a++) {
-    Uuid u;
-    std::memcpy(u.data(), actors + 16ull * a, 16);
-    auto it = c->slot_of.find(u);
-    if (it != c->slot_of.end()) (*e0)[a] = c->nov[it->second];
-  }
+  writer_versions_of(c, actors, m, e0);
   // d_shard: writers [16m] | e0 [8m] | cand [8m] | vmaxp1 [8m] | run_count [4m] | has_ge [4m] | bad
   hipError_t e;
   if ((e = c->d_shard.reserve(48ull * m + 64))) return ctx->hip_fail(e, "shard scratch");
@@ -77,6 +130,74 @@ int stage_writers(ce_core* c, const uint8_t* actors, uint32_t m, std::vector<uin
   if ((e = hipMemcpyAsync(b + 16ull * m, c->h_shard.p, 8ull * m, hipMemcpyHostToDevice, ctx->stream)))
     return ctx->hip_fail(e, "shard e0");
   return CE_OK;
+}
+
+// The sharded ingest, the export of its pending batch and the commit for the kinds whose batch is
+// a dense array over the actor slots: u64[words], words = state_planes(kind) * cap (VClock /
+// GCounter one plane; PNCounter p at [slot], n at [slot + cap]).  The callers have checked the kind.
+uint64_t dense_words(const ce_core* c) { return (uint64_t)state_planes(c->kind) * c->cap; }
+
+int dense_ingest_sharded(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n, uint64_t blob_len,
+                         const uint8_t* actors, uint32_t m, const uint32_t* d_fa, const uint64_t* d_fv,
+                         const uint64_t* d_hi, int32_t* status) {
+  if ((n && (!d_blob || !d_offs || !d_fa || !d_fv)) || (m && !actors) || !d_hi)
+    return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  ce_ctx* ctx = c->ctx;
+  if (n) return ingest_ops_dev_sharded(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, d_hi, status);
+  // no file on this rank: the windows still set next_op_versions, and the pending batch is empty
+  c->pending = false;
+  std::vector<uint64_t> hi(m + 1);
+  hipError_t e;
+  if ((e = hipMemsetAsync(c->d_batch.p, 0, dense_words(c) * 8ull, ctx->stream)) ||
+      (e = hipMemcpyAsync(hi.data(), d_hi, (m + 1) * 8ull, hipMemcpyDeviceToHost, ctx->stream)) ||
+      (e = hipStreamSynchronize(ctx->stream)))
+    return ctx->hip_fail(e, "sharded ingest");
+  if (hi[m] & (kShardBad | kShardE0Mismatch)) return ctx->fail(CE_ERR_SHARD, "partition contract / e0");
+  c->pending_nov.clear();
+  for (uint32_t a = 0; a < m; a++) {
+    Uuid u;
+    std::memcpy(u.data(), actors + 16ull * a, 16);
+    auto it = c->slot_of.find(u);
+    const uint64_t e0 = it == c->slot_of.end() ? 0 : c->nov[it->second];
+    c->pending_nov.push_back({u, std::max(e0, hi[a])});
+  }
+  c->pending = true;
+  c->pending_gen = c->table_gen;
+  return (hi[m] & kShardGap) ? CE_ERR_OP_VERSION : CE_OK;
+}
+
+int dense_pending_export(ce_core* c, uint64_t* d_batch, uint64_t cap_words, int* ready) {
+  if (!d_batch || !ready) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  if (!c->pending || c->pending_gen != c->table_gen) return c->ctx->fail(CE_ERR_INVALID_ARG, "no pending batch");
+  // an actor outside the registered slots (the ingest inserted it, and may have grown the table
+  // past the caller's buffer): not exportable, and nothing is written
+  *ready = c->registered == c->size && dense_words(c) <= cap_words ? 1 : 0;
+  if (!*ready) return CE_OK;
+  hipError_t e;
+  if ((e = hipMemcpyAsync(d_batch, c->d_batch.p, dense_words(c) * 8ull, hipMemcpyDeviceToDevice, c->ctx->stream)) ||
+      (e = c->ctx->sync_spin()))
+    return c->ctx->hip_fail(e, "pending export");
+  return CE_OK;
+}
+
+int dense_pending_commit(ce_core* c, int accept, const uint64_t* d_import, uint64_t import_words) {
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  if (!c->pending) return c->ctx->fail(CE_ERR_INVALID_ARG, "no pending batch");
+  c->pending = false;
+  if (!accept) return CE_OK;  // another rank's batch failed: the state stays unchanged
+  if (c->pending_gen != c->table_gen) return c->ctx->fail(CE_ERR_INVALID_ARG, "actor table changed since the ingest");
+  if (d_import && import_words < dense_words(c))
+    return c->ctx->fail(CE_ERR_INVALID_ARG, "reduced batch shorter than the dense capacity");
+  const hipError_t e = launch_merge_max(c->ctx->stream, c->d_state.as<unsigned long long>(),
+                                        d_import ? reinterpret_cast<const unsigned long long*>(d_import)
+                                                 : c->d_batch.as<unsigned long long>(),
+                                        (uint32_t)dense_words(c));
+  if (e) return c->ctx->hip_fail(e, "pending commit");
+  return commit_pending_nov(c);
 }
 
 }  // namespace
@@ -191,12 +312,9 @@ int ce_shard_window_exact(uint32_t m, const uint64_t* e0, const uint32_t* fa, co
 int ce_core_writer_versions(ce_core* c, const uint8_t* actors, uint32_t m, uint64_t* e0_out) {
   if (!c || (m && (!actors || !e0_out))) return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
-  for (uint32_t a = 0; a < m; a++) {
-    Uuid u;
-    std::memcpy(u.data(), actors + 16ull * a, 16);
-    auto it = c->slot_of.find(u);
-    e0_out[a] = it == c->slot_of.end() ? 0 : c->nov[it->second];
-  }
+  std::vector<uint64_t> e0;
+  writer_versions_of(c, actors, m, &e0);
+  if (m) std::memcpy(e0_out, e0.data(), 8ull * m);
   return CE_OK;
 }
 
@@ -256,72 +374,37 @@ int ce_core_ingest_ops_device_sharded(ce_core* c, const uint8_t* d_blob, const u
                                       uint64_t blob_len, const uint8_t* actors, uint32_t m,
                                       const uint32_t* d_fa, const uint64_t* d_fv, const uint64_t* d_hi,
                                       int32_t* status) {
-  if (!c || (n && (!d_blob || !d_offs || !d_fa || !d_fv)) || (m && !actors) || !d_hi || no_dense_exchange(c->kind))
-    return CE_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
-  (void)hipSetDevice(c->ctx->device);
-  ce_ctx* ctx = c->ctx;
-  if (n) return ingest_ops_dev_sharded(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, d_hi, status);
-  // no file on this rank: the windows still set next_op_versions, and the pending batch is empty
-  c->pending = false;
-  std::vector<uint64_t> hi(m + 1);
-  hipError_t e;
-  if ((e = hipMemsetAsync(c->d_batch.p, 0, c->cap * 8ull, ctx->stream)) ||
-      (e = hipMemcpyAsync(hi.data(), d_hi, (m + 1) * 8ull, hipMemcpyDeviceToHost, ctx->stream)) ||
-      (e = hipStreamSynchronize(ctx->stream)))
-    return ctx->hip_fail(e, "sharded ingest");
-  if (hi[m] & (kShardBad | kShardE0Mismatch)) return ctx->fail(CE_ERR_SHARD, "partition contract / e0");
-  c->pending_nov.clear();
-  for (uint32_t a = 0; a < m; a++) {
-    Uuid u;
-    std::memcpy(u.data(), actors + 16ull * a, 16);
-    auto it = c->slot_of.find(u);
-    const uint64_t e0 = it == c->slot_of.end() ? 0 : c->nov[it->second];
-    c->pending_nov.push_back({u, std::max(e0, hi[a])});
-  }
-  c->pending = true;
-  c->pending_gen = c->table_gen;
-  return (hi[m] & kShardGap) ? CE_ERR_OP_VERSION : CE_OK;
+  if (!c || no_dense_exchange(c->kind)) return CE_ERR_INVALID_ARG;
+  return dense_ingest_sharded(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, d_hi, status);
 }
 
 int ce_core_pending_export(ce_core* c, uint64_t* d_batch, uint64_t cap_words, int* ready) {
-  if (!c || !d_batch || !ready || no_dense_exchange(c->kind)) return CE_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
-  if (!c->pending || c->pending_gen != c->table_gen) return c->ctx->fail(CE_ERR_INVALID_ARG, "no pending batch");
-  // an actor outside the registered slots (the ingest inserted it, and may have grown the table
-  // past the caller's buffer): not exportable, and nothing is written
-  *ready = c->registered == c->size && c->cap <= cap_words ? 1 : 0;
-  if (!*ready) return CE_OK;
-  hipError_t e;
-  if ((e = hipMemcpyAsync(d_batch, c->d_batch.p, c->cap * 8ull, hipMemcpyDeviceToDevice, c->ctx->stream)) ||
-      (e = c->ctx->sync_spin()))
-    return c->ctx->hip_fail(e, "pending export");
-  return CE_OK;
+  if (!c || no_dense_exchange(c->kind)) return CE_ERR_INVALID_ARG;
+  return dense_pending_export(c, d_batch, cap_words, ready);
 }
 
 int ce_core_pending_commit(ce_core* c, int accept, const uint64_t* d_import, uint64_t import_words) {
   if (!c || no_dense_exchange(c->kind)) return CE_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
-  (void)hipSetDevice(c->ctx->device);
-  if (!c->pending) return c->ctx->fail(CE_ERR_INVALID_ARG, "no pending batch");
-  c->pending = false;
-  if (!accept) return CE_OK;  // another rank's batch failed: the state stays unchanged
-  if (c->pending_gen != c->table_gen) return c->ctx->fail(CE_ERR_INVALID_ARG, "actor table changed since the ingest");
-  if (d_import && import_words < c->cap)
-    return c->ctx->fail(CE_ERR_INVALID_ARG, "reduced batch shorter than the dense capacity");
-  const hipError_t e = launch_merge_max(c->ctx->stream, c->d_state.as<unsigned long long>(),
-                                        d_import ? reinterpret_cast<const unsigned long long*>(d_import)
-                                                 : c->d_batch.as<unsigned long long>(),
-                                        c->cap);
-  if (e) return c->ctx->hip_fail(e, "pending commit");
-  for (auto& p : c->pending_nov) {  // next_op_versions.inc per applied file (lib.rs:537-538)
-    if (p.second == 0) continue;   // nothing applied and nothing known: no entry (VClock::get = 0)
-    uint32_t s;
-    int rc = insert_actor(c, p.first, &s);
-    if (rc) return rc;
-    c->nov[s] = std::max(c->nov[s], p.second);
-  }
-  return table_upload(c);
+  return dense_pending_commit(c, accept, d_import, import_words);
+}
+
+// CE_STATE_PNCOUNTER: the same three steps over both planes of the dense batch
+int ce_core_pn_ingest_ops_device_sharded(ce_core* c, const uint8_t* d_blob, const uint64_t* d_offs, uint32_t n,
+                                         uint64_t blob_len, const uint8_t* actors, uint32_t m,
+                                         const uint32_t* d_fa, const uint64_t* d_fv, const uint64_t* d_hi,
+                                         int32_t* status) {
+  if (!c || c->kind != CE_STATE_PNCOUNTER) return CE_ERR_INVALID_ARG;
+  return dense_ingest_sharded(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, d_hi, status);
+}
+
+int ce_core_pn_pending_export(ce_core* c, uint64_t* d_batch, uint64_t cap_words, int* ready) {
+  if (!c || c->kind != CE_STATE_PNCOUNTER) return CE_ERR_INVALID_ARG;
+  return dense_pending_export(c, d_batch, cap_words, ready);
+}
+
+int ce_core_pn_pending_commit(ce_core* c, int accept, const uint64_t* d_import, uint64_t import_words) {
+  if (!c || c->kind != CE_STATE_PNCOUNTER) return CE_ERR_INVALID_ARG;
+  return dense_pending_commit(c, accept, d_import, import_words);
 }
 
 }  // extern "C"

@@ -14,6 +14,13 @@ every rank's state unchanged (lib.rs:497-514), otherwise each rank commits the r
 A Dot naming an actor outside the registered slots sends every rank to the all-gather of
 serialized states instead.
 
+PNCounter<Uuid>: ingest_sharded as it is over a DevicePnShardOps -- the pending batch and the
+reduced one are both planes of the dense array (p, then n).
+
+LWWReg<u64, u64>: the same partition and gate (ingest_lwwreg_sharded); the pending batch is the
+share's winner with its (writer index, version), so one all-gather of a 32-byte record per rank
+gives every rank the whole batch's winner in the batch's apply order.
+
 GSet<u64>: the same partition and the same gate (ingest_gset_sharded); the pending batch is the
 set of members the committed set lacks, so after one small all-gather of every rank's outcome the
 ranks all-gather those members as plain u64 columns and each commits the others' (or none does).
@@ -467,16 +474,21 @@ class _DeviceShardBase:
 class DeviceShardOps(_DeviceShardBase):
     """The sharded-ingest steps of a VClock / GCounter crdtenc.Core: the pending batch is a dense
     array over the registered slots."""
+    planes = 1      # planes of the dense batch, capacity words each
+    calls = ""      # prefix of the core's three sharded calls
 
     def __init__(self, core, actors, files, offs, n, blob_len, fa, fv):
         super().__init__(core, actors, files, offs, n, blob_len, fa, fv)
-        self.dense = torch.empty(core.dense_capacity() + 2, dtype=torch.int64, device=self.device)
+        self.dense = torch.empty(self.planes * core.dense_capacity() + 2, dtype=torch.int64, device=self.device)
+
+    def _call(self, name):
+        return getattr(self.core, self.calls + name)
 
     def ingest(self):
-        r = self.core.ingest_ops_device_sharded(self.files.data_ptr(), self.offs.data_ptr(), self.n,
-                                                self.blob_len, self.actors, self.fa.data_ptr(),
-                                                self.fv.data_ptr(), self.hi.data_ptr(),
-                                                want_status=self.want_status)
+        r = self._call("ingest_ops_device_sharded")(self.files.data_ptr(), self.offs.data_ptr(), self.n,
+                                                    self.blob_len, self.actors, self.fa.data_ptr(),
+                                                    self.fv.data_ptr(), self.hi.data_ptr(),
+                                                    want_status=self.want_status)
         if self.want_status:
             r, self.status = r
         return r
@@ -491,14 +503,23 @@ class DeviceShardOps(_DeviceShardBase):
         if dense.dtype != torch.int64:
             raise TypeError("dense is an int64 view of u64")
         self._ordered()
-        return self.core.pending_export(dense.data_ptr(), dense.numel())
+        return self._call("pending_export")(dense.data_ptr(), dense.numel())
 
     def commit(self, accept, reduced=None):
         self._ordered()
         if reduced is None:
-            self.core.pending_commit(accept)
+            self._call("pending_commit")(accept)
         else:
-            self.core.pending_commit(accept, reduced.data_ptr(), reduced.numel())
+            self._call("pending_commit")(accept, reduced.data_ptr(), reduced.numel())
+
+
+class DevicePnShardOps(DeviceShardOps):
+    """The same steps of a CE_STATE_PNCOUNTER crdtenc.Core for ingest_sharded, through the
+    ce_core_pn_* calls: the pending batch is both planes of the dense array (p at [slot], n at
+    [slot + capacity]), so `dense` is 2 * capacity + 2 words -- the failure flags ride in the last
+    two -- and merge_dense stays the one collective."""
+    planes = 2
+    calls = "pn_"
 
 
 def contract_flags(stats):
@@ -696,3 +717,85 @@ def ingest_gset_sharded(ops, group=None):
     others = [r for r in range(world) if r != rank]
     ops.commit(True, [every[r * width: r * width + counts[r]] for r in others], [counts[r] for r in others])
     return rc, "members" + exact
+
+
+# ---------------------------------------------------------------------------------------------
+# LWWReg<u64, u64> partitioned by op-file address: the same gate, one 32-byte record per rank
+# ---------------------------------------------------------------------------------------------
+LWW_NONE = (0, 0, (1 << 64) - 1, (1 << 64) - 1)
+_MAX_LWW_RECORDS = 64  # ce_core_lwwreg_pending_commit takes at most 64 remote records
+
+
+def lww_pick(records):
+    """The whole batch's winner among the shares' (marker, val, writer index, version) records:
+    the largest marker, then the lowest writer index, then the lowest version -- the first op with
+    the largest marker in the batch's apply order (shared writer order, version).  A record with
+    marker 0 never wins; LWW_NONE when none does.  The rule of ce_core_lwwreg_pending_commit."""
+    best = LWW_NONE
+    for r in records:
+        if r[0] and (-r[0], r[2], r[3]) < (-best[0], best[2], best[3]):
+            best = tuple(r)
+    return best
+
+
+class DeviceLwwShardOps(_DeviceShardBase):
+    """The sharded-ingest steps of a CE_STATE_LWWREG crdtenc.Core: the pending batch is the share's
+    winner with its (writer index, version)."""
+
+    def ingest(self):
+        r = self.core.lwwreg_ingest_ops_device_sharded(self.files.data_ptr(), self.offs.data_ptr(), self.n,
+                                                       self.blob_len, self.actors, self.fa.data_ptr(),
+                                                       self.fv.data_ptr(), self.hi.data_ptr(),
+                                                       want_status=self.want_status)
+        if self.want_status:
+            r, self.status = r
+        return r
+
+    def record(self):
+        rc, rec = self.core.lwwreg_pending_record()
+        if rc:
+            raise RuntimeError("lwwreg_pending_record failed: %d" % rc)
+        return rec
+
+    def commit(self, accept, recs=()):
+        rc = self.core.lwwreg_pending_commit(accept, recs)
+        if rc:
+            raise RuntimeError("lwwreg_pending_commit failed: %d" % rc)
+
+
+def ingest_lwwreg_sharded(ops, group=None):
+    """read_remote_ops (crdt-enc/src/lib.rs:471-547) of an LWWReg<u64, u64> over a batch
+    partitioned across the ranks by op-file address.  `ops`: a DeviceLwwShardOps (or the CPU test's
+    twin).  Every rank ends with the state the reference reaches folding the whole batch in (shared
+    writer order, version) order, ties included: each share's winner travels with its (writer
+    index, version), and every rank picks the best of them in that order.  One collective after
+    the gate's: an all-gather of [failure code, marker, val, writer, version] per rank.  Returns
+    (rc, path): rc 0, CE_ERR_OP_VERSION (the fold stopped at a gap; the files before it are folded
+    on every rank) or the failing status (every rank's state unchanged); path "record" |
+    "rejected" | "refused", plus "+exact" when the windows came from the gathered metadata."""
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    if world - 1 > _MAX_LWW_RECORDS:
+        raise ValueError("ce_core_lwwreg_pending_commit takes at most %d remote records" % _MAX_LWW_RECORDS)
+    # 1) the gate: ingest_sharded's
+    exact = _agree_windows(ops, group)
+    if exact is None:
+        return ERR_SHARD, "refused"
+    # 2) this rank's share, its winner left pending
+    rc = ops.ingest()
+    failed = rc not in (0, ERR_OP_VERSION)
+    # 3) the outcome and the record: a rank that failed locally still takes the collective
+    dev = getattr(ops, "device", torch.device("cpu"))
+    if dist.get_backend(group) == "gloo":
+        dev = torch.device("cpu")
+    rec = LWW_NONE if failed else ops.record()
+    wrap = [x - (1 << 64) if x >= (1 << 63) else x for x in rec]       # u64 as int64 bits
+    mine = torch.tensor([rc if failed else 0] + wrap, dtype=torch.int64, device=dev)
+    got = _all_gather_flat(mine, group=group).cpu().tolist()
+    codes = got[0::5]
+    if any(codes):
+        if not failed:
+            ops.commit(False)
+        return max(codes), "rejected" + exact
+    others = [tuple(x & 0xFFFFFFFFFFFFFFFF for x in got[5 * r + 1: 5 * r + 5]) for r in range(world) if r != rank]
+    ops.commit(True, others)
+    return rc, "record" + exact

@@ -119,6 +119,13 @@ int ce_ctx_prim_sort_pairs_u32(ce_ctx *ctx, const uint32_t *d_kin, uint32_t *d_k
                                const uint32_t *d_vin, uint32_t *d_vout, uint32_t n, int bits);
 int ce_ctx_prim_sort_pairs_u64(ce_ctx *ctx, const uint64_t *d_kin, uint64_t *d_kout,
                                const uint32_t *d_vin, uint32_t *d_vout, uint32_t n, int bits);
+/* The sharded LWWReg ingest's reduce (k_lww_reduce_keyed and its final stage, at the product grid
+ * or CE_TEST_GRID_CAP): d_rec holds n records {marker, val}, d_fa / d_fv their (writer index,
+ * version); out (host memory) = {marker, val, fa, fv} of the record with the largest marker, then
+ * the lowest fa, then the lowest fv, then the lowest index; {0, 0, ~0, ~0} when every marker is 0
+ * or n = 0 (nothing launched). */
+int ce_ctx_prim_lww_reduce_keyed(ce_ctx *ctx, const uint64_t *d_rec, const uint32_t *d_fa,
+                                 const uint64_t *d_fv, uint32_t n, uint64_t out[4]);
 
 /* ---------------------------------------------------------------------------------------- */
 /* Cryptor: XChaCha20-Poly1305 EncHandler on the GPU                                          */
@@ -243,8 +250,10 @@ enum ce_state_kind {
                             ce_core_import_dense, ce_core_ingest_ops_device_sharded,
                             ce_core_pending_export and ce_core_pending_commit return
                             CE_ERR_INVALID_ARG and touch nothing (ce_core_export_columns_device
-                            as for any non-Orswot kind).  Ranks exchange
-                            ce_core_state_bytes_device / ce_core_merge_state_device instead.     */
+                            as for any non-Orswot kind): their dense buffers are one plane.  Its
+                            own sharded ingest over both planes is ce_core_pn_ingest_ops_device_
+                            sharded with ce_core_pn_pending_export / _commit below; whole states
+                            travel as ce_core_state_bytes_device / ce_core_merge_state_device.  */
   CE_STATE_GSET = 5,     /* GSet<u64> {value: BTreeSet<u64>}: op = a member (an op file is a
                             Vec<u64>, any non-negative msgpack integer form).  The members live in
                             a device hash set (CE_GSET_CAP=<slots>: its starting capacity, read
@@ -274,10 +283,14 @@ enum ce_state_kind {
                             the call's file order; the reference merges them in completion order
                             (buffer_unordered, lib.rs:452) and so leaves a tie between two state
                             files unspecified.  A rejected batch leaves the register and
-                            next_op_versions as they were.  Entry points and the multi-GPU
-                            answers as for CE_STATE_PNCOUNTER: ranks exchange state bytes -- an
-                            address partition of the op files would break the apply order that
-                            ties depend on, so this kind has no sharded ingest.  The state is two
+                            next_op_versions as they were.  Entry points as for
+                            CE_STATE_PNCOUNTER; the dense exchange and the three generic sharded
+                            calls return CE_ERR_INVALID_ARG.  Its own sharded ingest is
+                            ce_core_lwwreg_ingest_ops_device_sharded with ce_core_lwwreg_pending_
+                            record / _commit below: across ranks the batch's apply order is
+                            (index in the shared writer list, version), every share's winner
+                            travels with that address, and the best of them in that order is the
+                            whole batch's winner, ties included.  The state is two
                             integers: state files, ce_core_merge_state[_device] and the writer
                             run on the host.  ce_core_lwwreg_read reads it.
                             ce_core_path_count keys: open_v3_lww (fused open launches),
@@ -564,6 +577,64 @@ int ce_core_gset_pending_members(ce_core *c, uint64_t *d_dst, uint64_t cap_membe
  * have been read on return. */
 int ce_core_gset_pending_commit(ce_core *c, int accept, const uint64_t *const *d_parts,
                                 const uint64_t *counts, uint32_t k);
+/* ---- CE_STATE_PNCOUNTER partitioned by op-file address (lib.rs:471-547).  ce_core_shard_stats,
+ * ce_core_shard_window and ce_core_writer_versions take a PNCounter core as they are; the three
+ * generic calls above keep refusing it (their dense buffers are one plane), and these take their
+ * place.  The pending batch is u64[2 * ce_core_dense_capacity()]: p at [slot], n at
+ * [slot + capacity], the layout of the committed state. ----
+ *
+ * read_remote_ops (lib.rs:471-547) over this rank's files with the windows as the gate: every file
+ * with e0 <= version < hi is folded, into both planes of a PENDING batch -- nothing is committed
+ * until ce_core_pn_pending_commit, so a failure on any rank can leave every rank's state unchanged
+ * (lib.rs:497-514).  Returns CE_OK, the lowest failing file's status, CE_ERR_OP_VERSION when the
+ * windows stop at a gap (the files before it are folded, lib.rs:527-531), or CE_ERR_SHARD (flags
+ * 1 or 4: nothing folded; compute the windows with ce_shard_window_exact and call again).  n = 0
+ * (a rank that owns no file): the windows still set next_op_versions and an empty pending batch
+ * exists.  While a batch is pending, ce_core_state_bytes*, ce_core_compact*, the content name and
+ * the reads see the committed state only; ce_core_apply_ops and ce_core_merge_state act on the
+ * committed state and leave the batch alone; any ops ingest (sharded or not) and ce_core_reset drop
+ * it.  Any other kind: CE_ERR_INVALID_ARG, nothing touched (all three calls). */
+int ce_core_pn_ingest_ops_device_sharded(ce_core *c, const uint8_t *d_blob, const uint64_t *d_offs,
+                                         uint32_t n, uint64_t blob_len, const uint8_t *actors,
+                                         uint32_t m, const uint32_t *d_fa, const uint64_t *d_fv,
+                                         const uint64_t *d_hi, int32_t *status);
+/* lib.rs:471-547: the pending batch, both planes, for the all_reduce(MAX); d_batch holds cap_words
+ * u64.  *ready = 0, and nothing is written, when the batch names an actor outside
+ * ce_core_register_actors or cap_words < 2 * ce_core_dense_capacity() (the actor table has grown
+ * since the caller sized d_batch): then commit it locally and exchange serialized states. */
+int ce_core_pn_pending_export(ce_core *c, uint64_t *d_batch, uint64_t cap_words, int *ready);
+/* lib.rs:471-547: accept: both planes of the state = max(state, d_import ? d_import (the reduced
+ * batch, import_words >= 2 * ce_core_dense_capacity()) : the local pending batch),
+ * next_op_versions from the windows (lib.rs:537-538); !accept: drop the pending batch. */
+int ce_core_pn_pending_commit(ce_core *c, int accept, const uint64_t *d_import, uint64_t import_words);
+/* ---- CE_STATE_LWWREG partitioned by op-file address (lib.rs:471-547), with the same three shard
+ * calls for the gate.  The whole batch's apply order is (index in the shared writer list, version),
+ * the order ce_shard_window_exact folds in; a share's winner keeps its place in it. ----
+ *
+ * read_remote_ops (lib.rs:471-547) over this rank's share: every file is opened, checked and
+ * decoded whatever the gate says; the gate is e0 <= version < d_hi[writer], decided on the device;
+ * the share's winner -- the largest marker, then the lowest writer index, then the lowest version,
+ * then the lowest index in its file -- stays PENDING: the register and next_op_versions are
+ * untouched.  Returns CE_OK; CE_ERR_OP_VERSION (the windows stop at a gap, the winner of the files
+ * before it pending); CE_ERR_SHARD (flags 1 or 4: nothing opened); or the lowest failing file's
+ * status -- then NO pending batch exists.  n = 0: the windows still set the pending
+ * next_op_versions and the pending record is "none".  The pending rules are the PNCounter calls'.
+ * Any other kind: CE_ERR_INVALID_ARG, nothing touched (all three calls). */
+int ce_core_lwwreg_ingest_ops_device_sharded(ce_core *c, const uint8_t *d_blob, const uint64_t *d_offs,
+                                             uint32_t n, uint64_t blob_len, const uint8_t *actors,
+                                             uint32_t m, const uint32_t *d_fa, const uint64_t *d_fv,
+                                             const uint64_t *d_hi, int32_t *status);
+/* lib.rs:471-547: the pending winner as {marker, val, writer index in the shared list, version}
+ * (host memory), {0, 0, ~0, ~0} when no applied op has a non-zero marker.  No pending batch:
+ * CE_ERR_INVALID_ARG, rec untouched. */
+int ce_core_lwwreg_pending_record(ce_core *c, uint64_t rec[4]);
+/* lib.rs:471-547: accept: the best of the local record and k <= 64 remote ones (recs: 4 words each,
+ * host memory; k = 0 with NULL allowed) -- largest marker, then lowest writer index, then lowest
+ * version -- goes through LWWReg::update (taken on a strictly larger marker only: a tie with the
+ * register keeps the incumbent), and next_op_versions come from the windows (lib.rs:537-538).
+ * !accept: the pending batch is dropped and nothing else changes.  k > 64, or NULL recs with
+ * k > 0: CE_ERR_INVALID_ARG, checked before anything is touched -- the batch stays pending. */
+int ce_core_lwwreg_pending_commit(ce_core *c, int accept, const uint64_t *recs, uint32_t k);
 /* next_op_versions.get(writer) for each of m writers (host) */
 int ce_core_writer_versions(ce_core *c, const uint8_t *actors, uint32_t m, uint64_t *e0_out);
 /* Host twins (CPU ranks, tests): ShardStats over host metadata; the windows from reduced stats;
@@ -581,8 +652,8 @@ int ce_shard_window_exact(uint32_t m, const uint64_t *e0, const uint32_t *fa, co
 /* makes of the merged state, without serializing it (ce_core_state_bytes) and parsing it back. */
 /* Every call takes the context lock, selects the core's device and answers for the COMMITTED   */
 /* state: a fold or merge queued without a host wait is settled first (as ce_core_settle); a    */
-/* GSet batch left pending by ce_core_gset_ingest_ops_device_sharded is no part of the answer   */
-/* until ce_core_gset_pending_commit; a poisoned dot-set core returns its error.  A state kind  */
+/* batch left pending by a sharded ingest (GSet, PNCounter, LWWReg) is no part of the answer    */
+/* until its commit; a poisoned dot-set core returns its error.  A state kind                   */
 /* the call does not serve: CE_ERR_INVALID_ARG, and no output is touched.  n = 0 (m = 0)        */
 /* succeeds, with NULL arrays allowed.                                                          */
 /* ---------------------------------------------------------------------------------------- */
