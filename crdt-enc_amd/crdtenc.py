@@ -72,7 +72,10 @@ EXPORTS = [
     "ce_core_pn_ingest_ops_device_sharded", "ce_core_pn_pending_export", "ce_core_pn_pending_commit",
     "ce_core_lwwreg_ingest_ops_device_sharded", "ce_core_lwwreg_pending_record", "ce_core_lwwreg_pending_commit",
     "ce_ctx_prim_lww_reduce_keyed",
+    "ce_core_gset_apply_bound", "ce_core_gset_apply_members_device", "ce_core_gset_apply_members",
 ]
+GSET_APPLY_NEW_ONLY = 1
+GSET_FILE_MEMBERS = 453     # the most members a written op file holds (one 4096-byte page at 9 bytes each)
 
 
 class _HostMem:
@@ -280,6 +283,14 @@ def _cbuf(b):
 
 def sealed_len(n):
     return lib().ce_cryptor_sealed_len(n)
+
+
+def gset_apply_bound(n, per_file=0):
+    """(rc, max_files, max_bytes) of Core.gset_apply_members_device over n members at per_file
+    members a file (0: 453): what d_file_offs (max_files + 1 words) and d_files must hold."""
+    f, b = ctypes.c_uint32(0), ctypes.c_uint64(0)
+    rc = lib().ce_core_gset_apply_bound(ctypes.c_uint64(n), ctypes.c_uint32(per_file), ctypes.byref(f), ctypes.byref(b))
+    return rc, f.value, b.value
 
 
 def _ptr(data):
@@ -1091,6 +1102,42 @@ class Core:
         cs = (ctypes.c_uint64 * max(k, 1))(*counts)
         return lib().ce_core_gset_pending_commit(self.p, 1 if accept else 0, ptrs if k else None,
                                                  cs if k else None, ctypes.c_uint32(k))
+
+    # ---- CE_STATE_GSET: op files written from a member column (Core::apply_ops without the host) ----
+    def gset_apply_members_device(self, d_members, n, d_files, cap, d_file_offs, per_file=0, flags=0,
+                                  nonces=None):
+        """The column d_members (device u64[n]) cut into op files of per_file members (0: 453),
+        sealed into d_files (device, cap bytes >= gset_apply_bound(n, per_file)[1]) with their
+        offsets in d_file_offs (device u64[max_files + 1]); stored when the core has storage,
+        inserted, next_op_versions bumped once a file.  nonces: one 24-byte nonce a file (None: the
+        OS RNG).  flags GSET_APPLY_NEW_ONLY: only the distinct members the set does not hold,
+        ascending.  Returns (rc, n_files, bytes)."""
+        nf, nb = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        rc = lib().ce_core_gset_apply_members_device(
+            self.p, ctypes.c_void_p(d_members) if d_members else None, ctypes.c_uint64(n),
+            ctypes.c_uint32(per_file), ctypes.c_uint32(flags),
+            _cbuf(b"".join(nonces)) if nonces is not None else None,
+            ctypes.c_void_p(d_files) if d_files else None, ctypes.c_uint64(cap),
+            ctypes.c_void_p(d_file_offs) if d_file_offs else None, ctypes.byref(nf), ctypes.byref(nb))
+        return rc, nf.value, nb.value
+
+    def gset_apply_members(self, members, per_file=0, flags=0, nonces=None):
+        """gset_apply_members_device over a host column (anything numpy reads as u64): returns
+        (rc, [op file bytes])."""
+        import numpy as np
+        import struct
+        col, cp = _np_ptr(members, np.uint64)
+        fb, fo = Buf(), Buf()
+        nf = ctypes.c_uint32(0)
+        rc = lib().ce_core_gset_apply_members(
+            self.p, cp if len(col) else None, ctypes.c_uint64(len(col)), ctypes.c_uint32(per_file),
+            ctypes.c_uint32(flags), _cbuf(b"".join(nonces)) if nonces is not None else None,
+            ctypes.byref(fb), ctypes.byref(fo), ctypes.byref(nf))
+        if rc:
+            return rc, None
+        blob, fofs = _take(fb), _take(fo)
+        o = struct.unpack("<%dQ" % (nf.value + 1), fofs)
+        return 0, [blob[o[i]:o[i + 1]] for i in range(nf.value)]
 
     # ---- CE_STATE_PNCOUNTER partitioned by op-file address (shard.ingest_sharded over a
     # shard.DevicePnShardOps): the dense calls' contracts over both planes ----

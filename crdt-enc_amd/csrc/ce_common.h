@@ -324,12 +324,12 @@ CE_HD int32_t parse_envelope(const uint8_t* enc, uint64_t enc_len, Envelope* e) 
 }
 
 // canonical envelope size produced by EncHandler::encrypt (xchacha lib.rs:59-67)
-CE_HD uint64_t bin_hdr_len(uint64_t l) { return l <= 0xff ? 2 : (l <= 0xffff ? 3 : 5); }
-CE_HD uint64_t encbox_len(uint64_t clear_len) {
+CE_HD constexpr uint64_t bin_hdr_len(uint64_t l) { return l <= 0xff ? 2 : (l <= 0xffff ? 3 : 5); }
+CE_HD constexpr uint64_t encbox_len(uint64_t clear_len) {
   const uint64_t ct = clear_len + 16;
   return 1 + 6 + 2 + 24 + 9 + bin_hdr_len(ct) + ct;
 }
-CE_HD uint64_t sealed_len(uint64_t clear_len) {
+CE_HD constexpr uint64_t sealed_len(uint64_t clear_len) {
   const uint64_t eb = encbox_len(clear_len);
   return 1 + 2 + 16 + bin_hdr_len(eb) + eb;
 }

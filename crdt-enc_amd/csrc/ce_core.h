@@ -334,6 +334,12 @@ int gs_merge_states_device(ce_core* c, const uint8_t* base, const std::vector<ui
 int gs_contains_device(ce_core* c, const uint64_t* d_members, uint64_t n, uint8_t* d_out);
 int gs_set_len(ce_core* c, uint64_t* n);
 int gs_members_device(ce_core* c, uint64_t* d_dst, uint64_t cap, uint64_t* n);
+// Core::apply_ops over a member column in HBM cut into files of per_file members
+// (ce_core_gset_apply_members_device, whose refusals the caller has checked): sized, encoded and
+// sealed on the device into d_files / d_file_offs, then stored, inserted and bumped
+int gs_apply_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, uint32_t per_file, uint32_t flags,
+                            const uint8_t* nonces, uint8_t* d_files, uint64_t* d_file_offs, uint32_t* n_files,
+                            uint64_t* bytes);
 // Vec<u64> as rmp-serde reads it (any non-negative integer form); false: CE_ERR_DECODE
 bool parse_gset_ops(const uint8_t* p, size_t n, std::vector<uint64_t>* out);
 // GSet { value: BTreeSet<u64> }: the reader (any order, duplicates) and the canonical writer

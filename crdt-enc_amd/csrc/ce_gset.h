@@ -100,4 +100,35 @@ hipError_t launch_gs_widths(hipStream_t s, const unsigned long long* v, uint32_t
 hipError_t launch_gs_write(hipStream_t s, const unsigned long long* v, const uint32_t* off, uint32_t n, uint8_t* out,
                            unsigned long long* clear_len_at, uint64_t head_len);
 
+// ---- the op-file writer (ce_gset_write.hip): a member column cut into files of per_file members
+// (the last may be shorter), file i's clear text = data version || array header || its members,
+// each in its smallest form.  per_file <= kGsFileMembers, so a clear text is at most one page.
+static constexpr uint32_t kGsFileMembers = 453;  // cf members whose clear text fills a 4096-byte page
+struct GsFilesArgs {
+  const unsigned long long* members;  // [n]
+  unsigned long long n;
+  uint32_t per_file;
+  uint32_t n_files;            // ceil(n / per_file) > 0
+  uint32_t* clen;              // [n_files + 1] clear lengths, clen[n_files] = 0 (the size pass)
+  uint32_t* xlen;              // [n_files + 1] a sealed file's bytes past its clear text and kGsSealBase
+  const uint32_t* coff;        // [n_files + 1] exclusive sums of clen (the encoder)
+  const uint32_t* xoff;        //               and of xlen
+  uint8_t dv[16];              // the data version
+  uint8_t* clear;              // the clear texts back to back, 16-byte aligned
+  unsigned long long* offs;    // [n_files + 1] clear offsets for the seal
+  unsigned long long* file_offs;  // [n_files + 1] sealed offsets: coff + i * kGsSealBase + xoff
+};
+// the least a sealed file adds to its clear text: the outer version and an envelope whose two bin
+// headers are bin8
+static constexpr uint64_t kGsSealBase = 16 + sealed_len(0);
+hipError_t launch_gs_file_sizes(hipStream_t s, const GsFilesArgs& a);
+// grid_cap: the most blocks to launch (0: the default)
+hipError_t launch_gs_files_encode(hipStream_t s, const GsFilesArgs& a, uint32_t grid_cap);
+// CE_GSET_APPLY_NEW_ONLY over the sorted column s[0..n): keep[i] = 1 where s[i] is the first of
+// its run and t does not hold it, keep[n] = 0; then, with pos = the exclusive scan of keep over
+// n + 1 words, the kept members in order into out (pos[n] of them)
+hipError_t launch_gs_new_mark(hipStream_t s, GsTable t, const unsigned long long* sorted, uint32_t n, uint32_t* keep);
+hipError_t launch_gs_new_compact(hipStream_t s, const unsigned long long* sorted, const uint32_t* keep,
+                                 const uint32_t* pos, uint32_t n, unsigned long long* out);
+
 }  // namespace ce

@@ -355,11 +355,7 @@ __global__ __launch_bounds__(256) void k_gs_contains(GsTable t, const unsigned l
   }
 }
 
-// the serializer: an element's encoded length (its smallest unsigned form), and the writer
-__device__ __forceinline__ uint32_t gs_width(unsigned long long v) {
-  return v <= 0x7f ? 1u : v <= 0xff ? 2u : v <= 0xffff ? 3u : v <= 0xffffffffull ? 5u : 9u;
-}
-
+// the serializer: an element's encoded length (gs_width: its smallest unsigned form), and the writer
 __global__ __launch_bounds__(256) void k_gs_widths(const unsigned long long* v, uint32_t n, uint32_t* w) {
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) w[i] = gs_width(v[i]);
 }

@@ -15,6 +15,10 @@
 // stays PENDING; the ranks exchange its members as u64 columns (ce_core_gset_pending_members) and
 // each commits its own batch table and the others' columns, or every rank drops its batch
 // (ce_core_gset_pending_commit).
+//
+// Written from HBM (ce_core_gset_apply_members[_device]): Core::apply_ops over a member column cut
+// into one-page op files, sized and encoded by ce_gset_write.hip, sealed by device_seal into the
+// caller's buffer, then stored, inserted into the committed table and counted in next_op_versions.
 #include <algorithm>
 #include <cstring>
 
@@ -38,6 +42,10 @@ struct GsState {
   DevBuf rd;
   HostBuf h_rd;                  // pinned: the heads' prefixes, the descriptors' upload, the run table
   uint64_t head_hint = 1u << 14;  // state head prefix to download (gs_merge_states_device)
+  // the op-file writer (gs_apply_members_device): per file, u32 clen | xlen | coff | xoff and the
+  // seal's u64 clear offsets (n_files + 1 of each); the filter's u32 keep | pos (n + 1 of each);
+  // the host twin's uploaded column, sealed files and offsets
+  DevBuf wr, filt, up_col, up_files, up_offs;
 };
 
 void gs_free(GsState* g) { delete g; }
@@ -672,6 +680,178 @@ int gs_compact_device(ce_core* c, std::vector<uint8_t> head, const uint8_t* oute
   return CE_OK;
 }
 
+// ---- the op-file writer: Core::apply_ops (lib.rs:666-722) over a member column in HBM ----
+
+namespace {
+
+constexpr uint64_t arr_hdr_len(uint64_t cnt) { return cnt <= 15 ? 1 : 3; }  // (cnt <= kGsFileMembers)
+
+// a column of n members at per_file (0: kGsFileMembers) members a file: the files, the most bytes
+// they take sealed (every member 9 bytes wide), and the clear texts' bound 19 F + 9 n; false:
+// per_file out of range, or more files than a u32 counts
+bool apply_bound(uint64_t n, uint32_t* per_file, uint32_t* files, uint64_t* bytes, uint64_t* clear_bound) {
+  if (*per_file == 0) *per_file = kGsFileMembers;
+  if (*per_file > kGsFileMembers) return false;
+  const uint64_t pf = *per_file, full = n / pf, rem = n % pf, F = full + (rem ? 1 : 0);
+  if (F > 0xffffffffull) return false;
+  *files = (uint32_t)F;
+  *bytes = full * (16 + sealed_len(16 + arr_hdr_len(pf) + 9 * pf)) +
+           (rem ? 16 + sealed_len(16 + arr_hdr_len(rem) + 9 * rem) : 0);
+  *clear_bound = 19 * F + 9 * n;
+  return true;
+}
+
+// what both forms refuse before anything is touched; *per_file normalised, *max_bytes the bound
+int apply_check(ce_core* c, uint64_t n, uint32_t* per_file, uint32_t flags, uint32_t* max_files, uint64_t* max_bytes) {
+  ce_ctx* ctx = c->ctx;
+  if (c->kind != CE_STATE_GSET) return ctx->fail(CE_ERR_INVALID_ARG, "gset apply: not a GSet core");
+  uint64_t clear_bound = 0;
+  if (!apply_bound(n, per_file, max_files, max_bytes, &clear_bound))
+    return ctx->fail(CE_ERR_INVALID_ARG, "gset apply: per_file is 1..453 (0: 453)");
+  if (flags & ~(uint32_t)CE_GSET_APPLY_NEW_ONLY) return ctx->fail(CE_ERR_INVALID_ARG, "gset apply: unknown flags");
+  if (clear_bound >= (1ull << 32)) return ctx->fail(CE_ERR_INVALID_ARG, "gset apply: column too large for 32-bit offsets");
+  if (!c->has_key) return ctx->fail(CE_ERR_NO_KEY, "no latest key");
+  return CE_OK;
+}
+
+// CE_GSET_APPLY_NEW_ONLY: the column's distinct members the committed table does not hold,
+// ascending, into g->col; *m = how many (the one word the host reads)
+int filter_new(ce_core* c, const uint64_t* d_members, uint32_t n, uint32_t* m) {
+  ce_ctx* ctx = c->ctx;
+  GsState* g = c->gs;
+  hipStream_t s = ctx->stream;
+  hipError_t e;
+  size_t sb = 0, cb = 0;
+  if ((e = g->sorted.reserve((size_t)n * 8 + 64)) || (e = g->col.reserve((size_t)n * 8 + 64)) ||
+      (e = g->vals.reserve((size_t)n * 8 + 64)) || (e = g->filt.reserve(((size_t)n + 1) * 8 + 64)) ||
+      (e = sort_pairs_u64(nullptr, sb, nullptr, nullptr, nullptr, nullptr, n, 64, s)) ||
+      (e = g->sort_tmp.reserve(sb + 256)) || (e = ds_excl_sum_u32(nullptr, cb, nullptr, nullptr, n + 1, s)) ||
+      (e = g->scan_tmp.reserve(cb + 256)))
+    return ctx->hip_fail(e, "gset apply filter");
+  sb = g->sort_tmp.cap;
+  cb = g->scan_tmp.cap;
+  unsigned long long* sorted = g->sorted.as<unsigned long long>();
+  uint32_t* vin = g->vals.as<uint32_t>();  // (the sort carries values; nobody reads them)
+  uint32_t* keep = g->filt.as<uint32_t>();
+  uint32_t* pos = keep + n + 1;
+  const int t = ctx->tbegin("gset_apply_filter");
+  if ((e = sort_pairs_u64(g->sort_tmp.p, sb, reinterpret_cast<const unsigned long long*>(d_members), sorted, vin,
+                          vin + n, n, 64, s)) ||
+      (e = launch_gs_new_mark(s, committed(g), sorted, n, keep)) ||
+      (e = ds_excl_sum_u32(g->scan_tmp.p, cb, keep, pos, n + 1, s)) ||
+      (e = launch_gs_new_compact(s, sorted, keep, pos, n, g->col.as<unsigned long long>())))
+    return ctx->hip_fail(e, "gset apply filter");
+  ctx->tend(t);
+  if ((e = hipMemcpyAsync(m, pos + n, 4, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+    return ctx->hip_fail(e, "gset apply filter");
+  if (*m > n) return ctx->fail(CE_ERR_DEVICE, "gset apply: more survivors than members");
+  return CE_OK;
+}
+
+}  // namespace
+
+// the arguments have passed apply_check; per_file is normalised and cap >= the bound's bytes
+int gs_apply_members_device(ce_core* c, const uint64_t* d_members, uint64_t n_in, uint32_t per_file, uint32_t flags,
+                            const uint8_t* nonces, uint8_t* d_files, uint64_t* d_file_offs, uint32_t* n_files,
+                            uint64_t* bytes) {
+  ce_ctx* ctx = c->ctx;
+  GsState* g = c->gs;
+  hipStream_t s = ctx->stream;
+  hipError_t e;
+  int rc;
+  const unsigned long long* col = reinterpret_cast<const unsigned long long*>(d_members);
+  uint32_t n = (uint32_t)n_in;  // (9 n < 2^32)
+  if (n && (flags & CE_GSET_APPLY_NEW_ONLY)) {
+    uint32_t m = 0;
+    if ((rc = filter_new(c, d_members, n, &m))) return rc;
+    c->path_counts["gset_apply_filtered"] += n - m;
+    col = g->col.as<unsigned long long>();
+    n = m;
+  }
+  const uint32_t F = (n + per_file - 1) / per_file;
+  if (F == 0) {  // nothing to write: the one offset, no file, no version
+    if ((e = hipMemsetAsync(d_file_offs, 0, 8, s)) || (e = stream_wait(s))) return ctx->hip_fail(e, "gset apply");
+    *n_files = 0;
+    *bytes = 0;
+    return CE_OK;
+  }
+  // room for every member before anything is sealed: the insert below cannot meet the load bound
+  uint32_t hm[kMetaWords];
+  if ((rc = read_meta(c, hm)) || (rc = ensure_committed(c, hm[kGsCount], n))) return rc;
+  const uint64_t U = 19ull * F + 9ull * n;
+  size_t cb = 0;
+  if ((e = ctx->blob.reserve(U + 64)) || (e = g->wr.reserve(24ull * (F + 1) + 64)) ||
+      (e = ctx->nonces.reserve(24ull * F)) || (e = ctx->outer_ver.reserve(64)) ||
+      (e = ds_excl_sum_u32(nullptr, cb, nullptr, nullptr, F + 1, s)) || (e = g->scan_tmp.reserve(cb + 256)))
+    return ctx->hip_fail(e, "gset apply reserve");
+  cb = g->scan_tmp.cap;
+  std::vector<uint8_t> nb;
+  if (!nonces) {
+    nb.resize(24ull * F);
+    os_random(nb.data(), nb.size());
+    nonces = nb.data();
+  }
+  GsFilesArgs a{};
+  a.members = col;
+  a.n = n;
+  a.per_file = per_file;
+  a.n_files = F;
+  a.offs = g->wr.as<unsigned long long>();
+  a.clen = reinterpret_cast<uint32_t*>(a.offs + F + 1);
+  a.xlen = a.clen + (F + 1);
+  uint32_t* coff = a.xlen + (F + 1);
+  uint32_t* xoff = coff + (F + 1);
+  a.coff = coff;
+  a.xoff = xoff;
+  std::memcpy(a.dv, c->current_data_version.data(), 16);
+  a.clear = ctx->blob.as<uint8_t>();
+  a.file_offs = reinterpret_cast<unsigned long long*>(d_file_offs);
+  if ((e = hipMemcpyAsync(ctx->nonces.p, nonces, 24ull * F, hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(ctx->outer_ver.p, kCoreVersion, 16, hipMemcpyHostToDevice, s)))
+    return ctx->hip_fail(e, "gset apply upload");
+  int t = ctx->tbegin("gset_apply_sizes");  // (the size pass and its two scans)
+  if ((e = launch_gs_file_sizes(s, a)) || (e = ds_excl_sum_u32(g->scan_tmp.p, cb, a.clen, coff, F + 1, s)) ||
+      (e = ds_excl_sum_u32(g->scan_tmp.p, cb, a.xlen, xoff, F + 1, s)))
+    return ctx->hip_fail(e, "gset apply sizes");
+  ctx->tend(t);
+  t = ctx->tbegin("gset_apply_encode");
+  if ((e = launch_gs_files_encode(s, a, test_grid_cap()))) return ctx->hip_fail(e, "gset apply encode");
+  ctx->tend(t);
+  // file i = CURRENT_VERSION || Cryptor::encrypt(clear_i) (lib.rs:682-695), straight into d_files
+  if ((rc = device_seal(ctx, a.clear, reinterpret_cast<const uint64_t*>(a.offs), F, U, ctx->outer_ver.as<uint8_t>(),
+                        ctx->nonces.as<uint8_t>(), d_files, d_file_offs, key_of(c))))
+    return rc;
+  uint64_t total = 0;
+  if ((e = hipMemcpyAsync(&total, d_file_offs + F, 8, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+    return ctx->hip_fail(e, "gset apply");
+  // everything is sealed: stored, inserted and bumped from here on
+  uint32_t slot;
+  if ((rc = insert_actor(c, c->local_actor, &slot))) return rc;
+  const uint64_t v0 = c->nov[slot];  // next_op_versions.get(actor) (lib.rs:703)
+  if (c->storage) {
+    std::vector<uint8_t> out(total);
+    std::vector<uint64_t> fo(F + 1);
+    if ((e = hipMemcpyAsync(out.data(), d_files, total, hipMemcpyDeviceToHost, s)) ||
+        (e = hipMemcpyAsync(fo.data(), d_file_offs, 8ull * (F + 1), hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+      return ctx->hip_fail(e, "gset apply download");
+    for (uint32_t i = 0; i < F; i++)
+      if ((rc = storage_store_op(c->storage, c->local_actor, v0 + i, out.data() + fo[i], fo[i + 1] - fo[i])))
+        return ctx->fail(rc, "failed writing ops file");
+  }
+  // state.apply(op) for op in ops (lib.rs:710-712): from the column, or the survivors, in HBM
+  t = ctx->tbegin("gset_apply_insert");
+  if ((e = launch_gs_insert(s, committed(g), col, n))) return ctx->hip_fail(e, "gset apply insert");
+  ctx->tend(t);
+  if ((e = stream_wait(s))) return ctx->hip_fail(e, "gset apply insert");  // (the column is the caller's)
+  slot = c->slot_of.at(c->local_actor);
+  c->nov[slot] = v0 + F;  // next_op_versions.inc(actor), once a file (lib.rs:714-715)
+  c->path_counts["gset_apply_device_files"] += F;
+  c->path_counts["gset_apply_device_members"] += n;
+  *n_files = F;
+  *bytes = total;
+  return table_upload(c);
+}
+
 namespace {
 
 // what the gate leaves for the commit: the writers' slots, next_op_versions after the applied
@@ -927,6 +1107,71 @@ int ce_core_gset_ingest_ops_device_sharded(ce_core* c, const uint8_t* d_blob, co
   std::lock_guard<std::recursive_mutex> lk(c->ctx->mu);
   (void)hipSetDevice(c->ctx->device);
   return gs_ingest_ops_sharded(c, d_blob, d_offs, n, blob_len, actors, m, d_fa, d_fv, d_hi, status);
+}
+
+int ce_core_gset_apply_bound(uint64_t n, uint32_t per_file, uint32_t* max_files, uint64_t* max_bytes) {
+  uint32_t files = 0;
+  uint64_t bytes = 0, clear_bound = 0;
+  if (!apply_bound(n, &per_file, &files, &bytes, &clear_bound)) return CE_ERR_INVALID_ARG;
+  if (max_files) *max_files = files;
+  if (max_bytes) *max_bytes = bytes;
+  return CE_OK;
+}
+
+int ce_core_gset_apply_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, uint32_t per_file,
+                                      uint32_t flags, const uint8_t* nonces, uint8_t* d_files, uint64_t cap,
+                                      uint64_t* d_file_offs, uint32_t* n_files, uint64_t* bytes) {
+  if (!c || (n && !d_members) || !d_file_offs || !n_files || !bytes) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  uint32_t max_files = 0;
+  uint64_t max_bytes = 0;
+  int rc = apply_check(c, n, &per_file, flags, &max_files, &max_bytes);
+  if (rc) return rc;
+  if (cap < max_bytes || (max_bytes && !d_files))
+    return c->ctx->fail(CE_ERR_INVALID_ARG, "gset apply: d_files below ce_core_gset_apply_bound");
+  return gs_apply_members_device(c, d_members, n, per_file, flags, nonces, d_files, d_file_offs, n_files, bytes);
+}
+
+int ce_core_gset_apply_members(ce_core* c, const uint64_t* members, uint64_t n, uint32_t per_file, uint32_t flags,
+                               const uint8_t* nonces, ce_buf* files, ce_buf* file_offs, uint32_t* n_files) {
+  if (!c || (n && !members) || !n_files) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  ce_ctx* ctx = c->ctx;
+  uint32_t max_files = 0;
+  uint64_t max_bytes = 0;
+  int rc = apply_check(c, n, &per_file, flags, &max_files, &max_bytes);
+  if (rc) return rc;
+  GsState* g = c->gs;
+  hipStream_t s = ctx->stream;
+  hipError_t e;
+  if ((e = g->up_col.reserve(n * 8 + 64)) || (e = g->up_files.reserve(max_bytes + 64)) ||
+      (e = g->up_offs.reserve(8ull * max_files + 64)) ||
+      (n && (e = hipMemcpyAsync(g->up_col.p, members, n * 8, hipMemcpyHostToDevice, s))))
+    return ctx->hip_fail(e, "gset apply upload");
+  uint32_t F = 0;
+  uint64_t total = 0;
+  if ((rc = gs_apply_members_device(c, g->up_col.as<uint64_t>(), n, per_file, flags, nonces, g->up_files.as<uint8_t>(),
+                                    g->up_offs.as<uint64_t>(), &F, &total)))
+    return rc;
+  std::vector<uint8_t> out(total);
+  std::vector<uint64_t> fo(F + 1);
+  if ((total && (e = hipMemcpyAsync(out.data(), g->up_files.p, total, hipMemcpyDeviceToHost, s))) ||
+      (e = hipMemcpyAsync(fo.data(), g->up_offs.p, 8ull * (F + 1), hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+    return ctx->hip_fail(e, "gset apply download");
+  if (files) {
+    files->data = (uint8_t*)malloc(out.size() ? out.size() : 1);
+    std::memcpy(files->data, out.data(), out.size());
+    files->len = out.size();
+  }
+  if (file_offs) {
+    file_offs->data = (uint8_t*)malloc(fo.size() * 8);
+    std::memcpy(file_offs->data, fo.data(), fo.size() * 8);
+    file_offs->len = fo.size() * 8;
+  }
+  *n_files = F;
+  return CE_OK;
 }
 
 int ce_core_gset_pending_members(ce_core* c, uint64_t* d_dst, uint64_t cap_members, uint64_t* n) {

@@ -261,7 +261,9 @@ enum ce_state_kind {
                             next_op_versions as they were.  Entry points and the multi-GPU
                             answers as for CE_STATE_PNCOUNTER, plus its own sharded ingest
                             (ce_core_gset_ingest_ops_device_sharded and the two ce_core_gset_
-                            pending_* calls below).  The state is written in BTreeSet
+                            pending_* calls below), and op files written from a member column
+                            in HBM (ce_core_gset_apply_members[_device] below: sized, encoded,
+                            sealed and inserted on the device).  The state is written in BTreeSet
                             order: collected, sorted, encoded and sealed on the device
                             (CE_HOST_COMPACT=1: encoded by the host writer, the cross-check).
                             ce_core_path_count keys: gset_fused_files (decoded inside the fused
@@ -271,7 +273,10 @@ enum ce_state_kind {
                             gset_states_host_read (state files the host parser took;
                             CE_HOST_STATES=1: every state file, uncounted),
                             gset_state_bytes_device (ce_core_state_bytes_device calls whose
-                            bytes never left HBM).                                              */
+                            bytes never left HBM), gset_apply_device_files,
+                            gset_apply_device_members and gset_apply_filtered (op files and
+                            members written by ce_core_gset_apply_members[_device], members its
+                            NEW_ONLY filter dropped).                                           */
   CE_STATE_LWWREG = 6    /* LWWReg<u64, u64> {val, marker}: op = LWWReg (an op file is a
                             Vec<LWWReg>), apply(op) = merge(op) = update(val, marker), taken
                             when the register's marker is strictly smaller.  An op or a state
@@ -577,6 +582,46 @@ int ce_core_gset_pending_members(ce_core *c, uint64_t *d_dst, uint64_t cap_membe
  * have been read on return. */
 int ce_core_gset_pending_commit(ce_core *c, int accept, const uint64_t *const *d_parts,
                                 const uint64_t *counts, uint32_t k);
+/* ---- CE_STATE_GSET: op files written from a member column in HBM (Core::apply_ops, lib.rs:666-722,
+ * without the host).  The column is cut, in order, into F = ceil(n / per_file) ops vectors of
+ * per_file members (the last may be shorter); each is one apply_ops(Vec<u64>) by the local actor,
+ * and the effect equals ce_core_apply_ops_batch over the same vectors.  File i =
+ * CURRENT_VERSION || Cryptor::encrypt(current_data_version || to_vec_named(Vec<u64>)): a fixarray
+ * or array16 header, every member in its smallest unsigned form (1, 2, 3, 5 or 9 bytes), sealed
+ * under the latest key with nonce i (nonces: host, 24 bytes a file; NULL: the OS RNG).  The files
+ * lie back to back in d_files (cap bytes), their F + 1 offsets go to d_file_offs (room for
+ * max_files + 1), *n_files = F and *bytes = the files' total.  With storage, file i is also stored
+ * as ops/<local actor>/<v0 + i> (one download of the files); the members are inserted into the
+ * committed set and next_op_versions of the local actor rises by F.  Everything is sealed before
+ * anything is stored, inserted or bumped.
+ * per_file: 1..453, 0 meaning 453 -- the most 9-byte members whose clear text fits one 4096-byte
+ * page, so every written file is one the readers' fused open decodes in LDS.
+ * n = 0: F = 0, d_file_offs[0] = 0, nothing else is written or bumped, CE_OK.
+ * CE_GSET_APPLY_NEW_ONLY: the ops are the column's distinct members the committed set does not
+ * hold, ascending, cut the same way (with_state(contains), then apply_ops); F may be 0.
+ * Refused before anything on the core changes, no output touched: CE_ERR_INVALID_ARG -- another
+ * kind, per_file > 453, unknown flags, cap below ce_core_gset_apply_bound's bytes, a column whose
+ * clear-text bound 19 F + 9 n reaches 2^32, a set that would pass 2^30 members; CE_ERR_NO_KEY.
+ * Host traffic without storage: the table's counts, *n_files and *bytes (NEW_ONLY: the survivor
+ * count); no member and no file byte.  The column has been read on return.
+ * ce_core_path_count keys: gset_apply_device_files, gset_apply_device_members,
+ * gset_apply_filtered (members NEW_ONLY dropped).  Timing regions: gset_apply_filter,
+ * gset_apply_sizes, gset_apply_encode, gset_apply_insert. ---- */
+enum ce_gset_apply_flags { CE_GSET_APPLY_NEW_ONLY = 1 };
+/* worst-case outputs for a column of n members at per_file members a file (every member 9 bytes);
+ * CE_ERR_INVALID_ARG: per_file > 453, or more than 2^32 - 1 files */
+int ce_core_gset_apply_bound(uint64_t n, uint32_t per_file, uint32_t *max_files, uint64_t *max_bytes);
+int ce_core_gset_apply_members_device(ce_core *c, const uint64_t *d_members, uint64_t n,
+                                      uint32_t per_file, uint32_t flags,
+                                      const uint8_t *nonces /* host, max_files*24, or NULL */,
+                                      uint8_t *d_files, uint64_t cap,
+                                      uint64_t *d_file_offs /* max_files+1 */, uint32_t *n_files,
+                                      uint64_t *bytes);
+/* the same over a host column: upload, the device call, files and offsets back as ce_bufs (either
+ * may be NULL) */
+int ce_core_gset_apply_members(ce_core *c, const uint64_t *members, uint64_t n, uint32_t per_file,
+                               uint32_t flags, const uint8_t *nonces, ce_buf *files,
+                               ce_buf *file_offs, uint32_t *n_files);
 /* ---- CE_STATE_PNCOUNTER partitioned by op-file address (lib.rs:471-547).  ce_core_shard_stats,
  * ce_core_shard_window and ce_core_writer_versions take a PNCounter core as they are; the three
  * generic calls above keep refusing it (their dense buffers are one plane), and these take their
