@@ -73,6 +73,7 @@ EXPORTS = [
     "ce_core_lwwreg_ingest_ops_device_sharded", "ce_core_lwwreg_pending_record", "ce_core_lwwreg_pending_commit",
     "ce_ctx_prim_lww_reduce_keyed",
     "ce_core_gset_apply_bound", "ce_core_gset_apply_members_device", "ce_core_gset_apply_members",
+    "ce_core_orswot_add_bound", "ce_core_orswot_add_members_device", "ce_core_orswot_add_members",
 ]
 GSET_APPLY_NEW_ONLY = 1
 GSET_FILE_MEMBERS = 453     # the most members a written op file holds (one 4096-byte page at 9 bytes each)
@@ -291,6 +292,16 @@ def gset_apply_bound(n, per_file=0):
     f, b = ctypes.c_uint32(0), ctypes.c_uint64(0)
     rc = lib().ce_core_gset_apply_bound(ctypes.c_uint64(n), ctypes.c_uint32(per_file), ctypes.byref(f), ctypes.byref(b))
     return rc, f.value, b.value
+
+
+def orswot_add_bound(n, per_op=0, ops_per_file=0):
+    """(rc, max_ops, max_files, max_bytes) of Core.orswot_add_members_device over n members at
+    per_op members an op (0: 1) and ops_per_file ops a file (0: 28 at one member an op, else the most
+    one page allows): what d_file_offs (max_files + 1 words) and d_files must hold."""
+    o, f, b = ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+    rc = lib().ce_core_orswot_add_bound(ctypes.c_uint64(n), ctypes.c_uint32(per_op), ctypes.c_uint32(ops_per_file),
+                                        ctypes.byref(o), ctypes.byref(f), ctypes.byref(b))
+    return rc, o.value, f.value, b.value
 
 
 def _ptr(data):
@@ -1132,6 +1143,43 @@ class Core:
         rc = lib().ce_core_gset_apply_members(
             self.p, cp if len(col) else None, ctypes.c_uint64(len(col)), ctypes.c_uint32(per_file),
             ctypes.c_uint32(flags), _cbuf(b"".join(nonces)) if nonces is not None else None,
+            ctypes.byref(fb), ctypes.byref(fo), ctypes.byref(nf))
+        if rc:
+            return rc, None
+        blob, fofs = _take(fb), _take(fo)
+        o = struct.unpack("<%dQ" % (nf.value + 1), fofs)
+        return 0, [blob[o[i]:o[i + 1]] for i in range(nf.value)]
+
+    # ---- CE_STATE_ORSWOT: Add-op files written from a member column (Core::apply_ops without the host) ----
+    def orswot_add_members_device(self, d_members, n, d_files, cap, d_file_offs, per_op=0, ops_per_file=0,
+                                  flags=0, nonces=None):
+        """The column d_members (device u64[n]) cut into Add ops of per_op members by the local
+        actor (counters from the clock's + 1) and the ops into files of ops_per_file ops, sealed into
+        d_files (device, cap bytes >= orswot_add_bound(...)[3]) with their offsets in d_file_offs
+        (device u64[max_files + 1]); stored when the core has storage, folded, next_op_versions
+        bumped once a file.  nonces: one 24-byte nonce a file (None: the OS RNG).  Returns
+        (rc, n_files, bytes)."""
+        nf, nb = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        rc = lib().ce_core_orswot_add_members_device(
+            self.p, ctypes.c_void_p(d_members) if d_members else None, ctypes.c_uint64(n),
+            ctypes.c_uint32(per_op), ctypes.c_uint32(ops_per_file), ctypes.c_uint32(flags),
+            _cbuf(b"".join(nonces)) if nonces is not None else None,
+            ctypes.c_void_p(d_files) if d_files else None, ctypes.c_uint64(cap),
+            ctypes.c_void_p(d_file_offs) if d_file_offs else None, ctypes.byref(nf), ctypes.byref(nb))
+        return rc, nf.value, nb.value
+
+    def orswot_add_members(self, members, per_op=0, ops_per_file=0, flags=0, nonces=None):
+        """orswot_add_members_device over a host column (anything numpy reads as u64): returns
+        (rc, [op file bytes])."""
+        import numpy as np
+        import struct
+        col, cp = _np_ptr(members, np.uint64)
+        fb, fo = Buf(), Buf()
+        nf = ctypes.c_uint32(0)
+        rc = lib().ce_core_orswot_add_members(
+            self.p, cp if len(col) else None, ctypes.c_uint64(len(col)), ctypes.c_uint32(per_op),
+            ctypes.c_uint32(ops_per_file), ctypes.c_uint32(flags),
+            _cbuf(b"".join(nonces)) if nonces is not None else None,
             ctypes.byref(fb), ctypes.byref(fo), ctypes.byref(nf))
         if rc:
             return rc, None

@@ -2252,6 +2252,57 @@ int ce_core_apply_ops_batch(ce_core* c, const uint8_t* ops, const uint64_t* offs
   return table_upload(c);
 }
 
+int ce_core_orswot_add_bound(uint64_t n, uint32_t per_op, uint32_t ops_per_file, uint64_t* max_ops,
+                             uint32_t* max_files, uint64_t* max_bytes) {
+  OwShape sh{};
+  if (!ow_shape(n, per_op, ops_per_file, &sh)) return CE_ERR_INVALID_ARG;
+  if (max_ops) *max_ops = sh.n_ops;
+  if (max_files) *max_files = sh.files;
+  if (max_bytes) *max_bytes = sh.bytes;
+  return CE_OK;
+}
+
+int ce_core_orswot_add_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, uint32_t per_op,
+                                      uint32_t ops_per_file, uint32_t flags, const uint8_t* nonces, uint8_t* d_files,
+                                      uint64_t cap, uint64_t* d_file_offs, uint32_t* n_files, uint64_t* bytes) {
+  if (!c || (n && !d_members) || !d_file_offs || !n_files || !bytes) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  OwShape sh{};
+  int rc = ds_add_check(c, n, per_op, ops_per_file, flags, &sh);
+  if (rc) return rc;
+  if (cap < sh.bytes || (sh.bytes && !d_files))
+    return c->ctx->fail(CE_ERR_INVALID_ARG, "orswot add: d_files below ce_core_orswot_add_bound");
+  return ds_add_members_device(c, d_members, n, sh, nonces, d_files, d_file_offs, n_files, bytes);
+}
+
+int ce_core_orswot_add_members(ce_core* c, const uint64_t* members, uint64_t n, uint32_t per_op, uint32_t ops_per_file,
+                               uint32_t flags, const uint8_t* nonces, ce_buf* files, ce_buf* file_offs,
+                               uint32_t* n_files) {
+  if (!c || (n && !members) || !n_files) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  OwShape sh{};
+  int rc = ds_add_check(c, n, per_op, ops_per_file, flags, &sh);
+  if (rc) return rc;
+  std::vector<uint8_t> out;
+  std::vector<uint64_t> fo;
+  uint32_t F = 0;
+  if ((rc = ds_add_members_host(c, members, n, sh, nonces, &out, &fo, &F))) return rc;
+  if (files) {
+    files->data = (uint8_t*)malloc(out.size() ? out.size() : 1);
+    std::memcpy(files->data, out.data(), out.size());
+    files->len = out.size();
+  }
+  if (file_offs) {
+    file_offs->data = (uint8_t*)malloc(fo.size() * 8);
+    std::memcpy(file_offs->data, fo.data(), fo.size() * 8);
+    file_offs->len = fo.size() * 8;
+  }
+  *n_files = F;
+  return CE_OK;
+}
+
 int ce_core_reset(ce_core* c) {
   if (!c) return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);

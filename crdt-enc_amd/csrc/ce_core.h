@@ -300,6 +300,27 @@ int ds_mvreg_read(ce_core* c, std::vector<uint64_t>* out);
 // Core::apply_ops for a local Vec<S::Op> (already validated by ds_check_ops)
 int ds_check_ops(ce_core* c, const uint8_t* ops, size_t len);
 int ds_apply_local_ops(ce_core* c, const uint8_t* ops, size_t len);
+// The Orswot add-op writer (ce_core_orswot_add_members[_device]): Core::apply_ops over a member
+// column cut into Add ops of per_op members by the local actor, ops_per_file ops a file.
+// ow_shape: the normalised pair (per_op 0: 1; ops_per_file 0: 28 at one member an op, else the
+// most the page allows) and the worst-case sizes; false when a file may pass one page or the files
+// do not fit a u32.  ds_add_check: everything either form refuses from its arguments alone.
+struct OwShape {
+  uint32_t per_op, opf;
+  uint64_t n_ops;
+  uint32_t files;
+  uint64_t bytes, clear;  // the sealed files' and the clear texts' worst case
+};
+bool ow_shape(uint64_t n, uint32_t per_op, uint32_t ops_per_file, OwShape* o);
+int ds_add_check(ce_core* c, uint64_t n, uint32_t per_op, uint32_t ops_per_file, uint32_t flags, OwShape* o);
+// the arguments have passed ds_add_check and d_files holds sh.bytes: reads the local actor's
+// counter (refusing a call that would pass 2^64 - 1), then sized, encoded and sealed on the device
+// into d_files / d_file_offs, then stored, folded and bumped
+int ds_add_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, const OwShape& sh, const uint8_t* nonces,
+                          uint8_t* d_files, uint64_t* d_file_offs, uint32_t* n_files, uint64_t* bytes);
+// the same over a host column: the files and their n_files + 1 offsets come back to the host
+int ds_add_members_host(ce_core* c, const uint64_t* members, uint64_t n, const OwShape& sh, const uint8_t* nonces,
+                        std::vector<uint8_t>* files, std::vector<uint64_t>* file_offs, uint32_t* n_files);
 
 // GSet<u64> (ce_gset_host.cpp): the members live in a device hash set; next_op_versions, the
 // actor table and the storage plumbing are ce_core.cpp's, as for every kind

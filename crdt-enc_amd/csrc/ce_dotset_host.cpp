@@ -25,6 +25,7 @@
 #include "ce_dotset.h"
 #include "ce_dotset_codec.h"
 #include "ce_dotset_io.h"
+#include "ce_orswot_write.h"
 
 namespace ce {
 
@@ -111,6 +112,10 @@ struct DsState {
   uint64_t state_gen = 1, read_gen = 0, read_len = 0;
   DevBuf read_flags, read_q, read_ans, read_qidx, read_ent, read_cnt, read_col, read_sorted;
   HostBuf read_host;
+  // the add-op writer (ds_add_members_device): the seal's u64 clear offsets (files + 1), then u32
+  // olen | ooff (ops + 1 of each) and clen | xlen | coff | xoff (files + 1 of each); the host
+  // twin's uploaded column, sealed files and offsets
+  DevBuf ow_wr, ow_col, ow_files, ow_offs;
 };
 
 void ds_free(DsState* d) { delete d; }
@@ -2542,6 +2547,242 @@ int ds_apply_local_ops(ce_core* c, const uint8_t* ops, size_t len) {
     return orswot_fold(c, tot, items, false);
   }
   return mvreg_fold_ops(c, (uint32_t)base.v[kCntRm], (uint32_t)tot.v[kCntRm]);
+}
+
+// ---------------------------------------------------------------------------------------
+// The add-op writer (ce_core_orswot_add_members[_device]): Core::apply_ops (lib.rs:666-722) over a
+// member column in HBM cut into Add ops by the local actor and the ops into one-page files, sized
+// and encoded by ce_orswot_write.hip, sealed by device_seal into the caller's buffer, then stored,
+// folded from columns filled on the device and counted in next_op_versions.
+// ---------------------------------------------------------------------------------------
+bool ow_shape(uint64_t n, uint32_t per_op, uint32_t opf, OwShape* o) {
+  if (per_op == 0) per_op = 1;
+  if (per_op > kOwPage) return false;  // (no such op fits a page; keeps the products below small)
+  const uint64_t op_full = ow_op_bound(per_op);
+  if (opf == 0) {
+    if (per_op == 1) {
+      opf = kDsFuseRegion >= 16 + 3 ? (uint32_t)((kDsFuseRegion - 16 - 3) / op_full) : 0;  // 28: the readers' LDS decode
+    } else {
+      opf = (uint32_t)((kOwPage - 16 - 3) / op_full);
+      if (opf < 16) opf = (uint32_t)std::min<uint64_t>(15, (kOwPage - 16 - 1) / op_full);
+    }
+  }
+  if (opf == 0 || opf > kOwPage || ow_file_bound(opf, per_op) > kOwPage) return false;
+  o->per_op = per_op;
+  o->opf = opf;
+  o->n_ops = (n + per_op - 1) / per_op;
+  const uint64_t F = (o->n_ops + opf - 1) / opf;
+  if (F > 0xffffffffull) return false;
+  o->files = (uint32_t)F;
+  o->bytes = o->clear = 0;
+  if (F == 0) return true;
+  // every file but the last holds opf full ops; the last op may be shorter, the last file hold fewer
+  const uint64_t rem = n % per_op, last_ops = o->n_ops - (F - 1) * opf;
+  const uint64_t full_clear = ow_file_bound(opf, per_op);
+  const uint64_t last_clear = 16 + ow_arr_hdr((uint32_t)last_ops) + (last_ops - 1) * op_full + (rem ? ow_op_bound(rem) : op_full);
+  o->clear = (F - 1) * full_clear + last_clear;
+  o->bytes = (F - 1) * (16 + sealed_len(full_clear)) + 16 + sealed_len(last_clear);
+  return true;
+}
+
+int ds_add_check(ce_core* c, uint64_t n, uint32_t per_op, uint32_t opf, uint32_t flags, OwShape* o) {
+  ce_ctx* ctx = c->ctx;
+  if (c->kind != CE_STATE_ORSWOT) return ctx->fail(CE_ERR_INVALID_ARG, "orswot add: not an Orswot core");
+  if (!ow_shape(n, per_op, opf, o))
+    return ctx->fail(CE_ERR_INVALID_ARG, "orswot add: a file of ops_per_file ops of per_op members may pass one page");
+  if (flags) return ctx->fail(CE_ERR_INVALID_ARG, "orswot add: unknown flags");
+  if (n >= (1ull << 32) || o->n_ops >= (1ull << 32) || o->clear >= (1ull << 32))
+    return ctx->fail(CE_ERR_INVALID_ARG, "orswot add: column too large for 32-bit offsets");
+  if (!c->has_key) return ctx->fail(CE_ERR_NO_KEY, "no latest key");
+  return CE_OK;
+}
+
+int ds_add_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, const OwShape& sh, const uint8_t* nonces,
+                          uint8_t* d_files, uint64_t* d_file_offs, uint32_t* n_files, uint64_t* bytes) {
+  ce_ctx* ctx = c->ctx;
+  DsState* d = c->ds;
+  hipStream_t s = ctx->stream;
+  hipError_t e;
+  int rc;
+  if ((rc = ds_settle(c))) return rc;
+  const uint32_t F = sh.files, n_ops = (uint32_t)sh.n_ops;
+  // c0 = clock.get(local actor), the one word the host reads before the files are sealed
+  uint64_t c0 = 0;
+  if (auto it = c->slot_of.find(c->local_actor); it != c->slot_of.end()) {
+    const uint32_t aid = actor_id_of_slot(c, it->second);
+    if (aid < d->clock_cap &&
+        ((e = hipMemcpyAsync(&c0, d->clock.as<unsigned long long>() + aid, 8, hipMemcpyDeviceToHost, s)) ||
+         (e = stream_wait(s))))
+      return ctx->hip_fail(e, "orswot add clock");
+  }
+  if (sh.n_ops > ~0ull - c0) return ctx->fail(CE_ERR_INVALID_ARG, "orswot add: the local actor's counter would pass 2^64 - 1");
+  if (F == 0) {  // nothing to write: the one offset, no file, no version
+    if ((e = hipMemsetAsync(d_file_offs, 0, 8, s)) || (e = stream_wait(s))) return ctx->hip_fail(e, "orswot add");
+    *n_files = 0;
+    *bytes = 0;
+    return CE_OK;
+  }
+  const uint64_t U = sh.clear;
+  size_t cb = 0;
+  if ((e = ctx->blob.reserve(U + 64)) || (e = d->ow_wr.reserve(8ull * (F + 1) + 8ull * (n_ops + 1) + 16ull * (F + 1) + 64)) ||
+      (e = ctx->nonces.reserve(24ull * F)) || (e = ctx->outer_ver.reserve(64)) ||
+      (e = ds_excl_sum_u32(nullptr, cb, nullptr, nullptr, std::max(n_ops, F) + 1, s)) || (e = d->cub_tmp.reserve(cb + 256)))
+    return ctx->hip_fail(e, "orswot add reserve");
+  cb = d->cub_tmp.cap;
+  std::vector<uint8_t> nb;
+  if (!nonces) {
+    nb.resize(24ull * F);
+    os_random(nb.data(), nb.size());
+    nonces = nb.data();
+  }
+  OwArgs a{};
+  a.members = reinterpret_cast<const unsigned long long*>(d_members);
+  a.n = n;
+  a.c0 = c0;
+  a.per_op = sh.per_op;
+  a.opf = sh.opf;
+  a.n_ops = n_ops;
+  a.n_files = F;
+  a.offs = d->ow_wr.as<unsigned long long>();
+  a.olen = reinterpret_cast<uint32_t*>(a.offs + F + 1);
+  uint32_t* ooff = a.olen + (n_ops + 1);
+  a.clen = ooff + (n_ops + 1);
+  a.xlen = a.clen + (F + 1);
+  uint32_t* coff = a.xlen + (F + 1);
+  uint32_t* xoff = coff + (F + 1);
+  a.ooff = ooff;
+  a.coff = coff;
+  a.xoff = xoff;
+  std::memcpy(a.dv, c->current_data_version.data(), 16);
+  {  // an op up to its counter, then a7 "members" (to_vec_named: structs as maps, the variant by name)
+    Wr w;
+    w.map(1);
+    w.str("Add");
+    w.map(2);
+    w.str("dot");
+    w.map(2);
+    w.str("actor");
+    w.bin(c->local_actor.data(), 16);
+    w.str("counter");
+    w.str("members");
+    if (w.b.size() != kOwFixedBytes) return ctx->fail(CE_ERR_DEVICE, "orswot add: op head");
+    std::memcpy(a.head, w.b.data(), kOwFixedBytes);
+  }
+  a.clear = ctx->blob.as<uint8_t>();
+  a.file_offs = reinterpret_cast<unsigned long long*>(d_file_offs);
+  if ((e = hipMemcpyAsync(ctx->nonces.p, nonces, 24ull * F, hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(ctx->outer_ver.p, kCoreVersion, 16, hipMemcpyHostToDevice, s)))
+    return ctx->hip_fail(e, "orswot add upload");
+  int t = ctx->tbegin("orswot_add_sizes");  // (the two size passes and their three scans)
+  if ((e = launch_ow_op_sizes(s, a)) || (e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.olen, ooff, n_ops + 1, s)) ||
+      (e = launch_ow_file_sizes(s, a)) || (e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.clen, coff, F + 1, s)) ||
+      (e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.xlen, xoff, F + 1, s)))
+    return ctx->hip_fail(e, "orswot add sizes");
+  ctx->tend(t);
+  t = ctx->tbegin("orswot_add_encode");
+  if ((e = launch_ow_encode(s, a, test_grid_cap()))) return ctx->hip_fail(e, "orswot add encode");
+  ctx->tend(t);
+  // file i = CURRENT_VERSION || Cryptor::encrypt(clear_i) (lib.rs:682-695), straight into d_files
+  if ((rc = device_seal(ctx, a.clear, reinterpret_cast<const uint64_t*>(a.offs), F, U, ctx->outer_ver.as<uint8_t>(),
+                        ctx->nonces.as<uint8_t>(), d_files, d_file_offs, key_of(c))))
+    return rc;
+  uint64_t total = 0;
+  if ((e = hipMemcpyAsync(&total, d_file_offs + F, 8, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+    return ctx->hip_fail(e, "orswot add");
+  // everything is sealed: stored, folded and bumped from here on
+  uint32_t slot;
+  if ((rc = insert_actor(c, c->local_actor, &slot))) return rc;
+  const uint64_t v0 = c->nov[slot];  // next_op_versions.get(actor) (lib.rs:703)
+  if (c->storage) {
+    std::vector<uint8_t> out(total);
+    std::vector<uint64_t> fo(F + 1);
+    if ((e = hipMemcpyAsync(out.data(), d_files, total, hipMemcpyDeviceToHost, s)) ||
+        (e = hipMemcpyAsync(fo.data(), d_file_offs, 8ull * (F + 1), hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+      return ctx->hip_fail(e, "orswot add download");
+    for (uint32_t i = 0; i < F; i++)
+      if ((rc = storage_store_op(c->storage, c->local_actor, v0 + i, out.data() + fo[i], fo[i + 1] - fo[i])))
+        return ctx->fail(rc, "failed writing ops file");
+  }
+  // state.apply(op) for op in ops (lib.rs:710-712): the fold's add columns filled from the column
+  // in HBM.  Short ops go in as they are, one add an op.  Long ops go in as one add a member, the
+  // members of an op sharing its dot: the same entries and clock, but the fold's kernels take a
+  // lane an add, and 446 members walked by one lane left the chip idle.  Either way one run of one
+  // actor whose counters never fall from c0 + 1: the fill writes the applied flags and exclusive
+  // maxima of the sort-free path itself, and the flags that select it are set here for this batch
+  // and cleared behind the fold (never an earlier ingest's).  CE_DS_SORT_ADDS / CE_DS_NO_MONO: the
+  // sorted path, which derives the flags from the counters and so takes one add an op
+  const bool mono = !getenv("CE_DS_SORT_ADDS") && !getenv("CE_DS_NO_MONO");
+  const uint32_t span = mono && sh.per_op >= kOwGroupOps ? 1u : sh.per_op;
+  const uint32_t n_add = span == 1 ? (uint32_t)n : n_ops;
+  Counts tot;
+  tot.v[kCntAdd] = n_add;
+  tot.v[kCntAddM] = n;
+  if ((rc = table_upload(c)) || (rc = ensure_clock(c)) || (rc = reserve_ops(c, tot))) return rc;
+  if ((e = d->applied.reserve(n_add + 64)) || (e = d->excl.reserve(n_add * 8ull))) return ctx->hip_fail(e, "applied");
+  DsOps o = ops_view(d);
+  OwCols oc{};
+  oc.members = a.members;
+  oc.n = n;
+  oc.c0 = c0;
+  oc.per_op = sh.per_op;
+  oc.span = span;
+  oc.n_add = n_add;
+  oc.actor_id = actor_id_of_slot(c, slot);
+  oc.add_actor = o.add_actor;
+  oc.add_ctr = o.add_ctr;
+  oc.add_mbeg = o.add_mbeg;
+  oc.add_mem = o.add_mem;
+  oc.rm_cbeg = o.rm_cbeg;
+  oc.rm_mbeg = o.rm_mbeg;
+  oc.applied = d->applied.as<uint8_t>();
+  oc.excl = d->excl.as<unsigned long long>();
+  t = ctx->tbegin("orswot_add_cols");
+  if ((e = launch_ow_cols(s, oc))) return ctx->hip_fail(e, "orswot add columns");
+  ctx->tend(t);
+  d->adds_mono = mono;
+  d->adds_mono_n = mono ? n_add : 0;
+  rc = orswot_fold(c, tot, 0, mono);
+  d->adds_mono = false;  // (they described this batch's columns only)
+  d->adds_mono_n = 0;
+  // the closing counts, and the column is the caller's again; a failure from the fold on leaves
+  // tables that no longer describe a state
+  if (!rc) rc = ds_settle(c);
+  if (rc) {
+    d->poisoned = true;
+    return rc;
+  }
+  slot = c->slot_of.at(c->local_actor);
+  c->nov[slot] = v0 + F;  // next_op_versions.inc(actor), once a file (lib.rs:714-715)
+  c->path_counts["orswot_add_device_files"] += F;
+  c->path_counts["orswot_add_device_ops"] += n_ops;
+  c->path_counts["orswot_add_device_members"] += n;
+  *n_files = F;
+  *bytes = total;
+  return table_upload(c);
+}
+
+int ds_add_members_host(ce_core* c, const uint64_t* members, uint64_t n, const OwShape& sh, const uint8_t* nonces,
+                        std::vector<uint8_t>* out, std::vector<uint64_t>* fo, uint32_t* n_files) {
+  ce_ctx* ctx = c->ctx;
+  DsState* d = c->ds;
+  hipStream_t s = ctx->stream;
+  hipError_t e;
+  if ((e = d->ow_col.reserve(n * 8 + 64)) || (e = d->ow_files.reserve(sh.bytes + 64)) ||
+      (e = d->ow_offs.reserve(8ull * (sh.files + 1ull) + 64)) ||
+      (n && (e = hipMemcpyAsync(d->ow_col.p, members, n * 8, hipMemcpyHostToDevice, s))))
+    return ctx->hip_fail(e, "orswot add upload");
+  uint32_t F = 0;
+  uint64_t total = 0;
+  if (int rc = ds_add_members_device(c, d->ow_col.as<uint64_t>(), n, sh, nonces, d->ow_files.as<uint8_t>(),
+                                     d->ow_offs.as<uint64_t>(), &F, &total))
+    return rc;
+  out->resize(total);
+  fo->resize(F + 1);
+  if ((total && (e = hipMemcpyAsync(out->data(), d->ow_files.p, total, hipMemcpyDeviceToHost, s))) ||
+      (e = hipMemcpyAsync(fo->data(), d->ow_offs.p, 8ull * (F + 1), hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+    return ctx->hip_fail(e, "orswot add download");
+  *n_files = F;
+  return CE_OK;
 }
 
 // Compaction of an Orswot state without bringing the entries to the host: the clear text

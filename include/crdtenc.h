@@ -241,7 +241,10 @@ enum ce_state_kind {
   CE_STATE_ORSWOT = 2,   /* Orswot<u64, Uuid>: op = orswot::Op {Add{dot, members}, Rm{clock,
                             members}}; entries/deferred serialized in canonical order (members
                             ascending, deferred clocks by their msgpack bytes): the reference's
-                            HashMap order is random                           */
+                            HashMap order is random.  Add-op files are also
+                            written from a member column in HBM
+                            (ce_core_orswot_add_members[_device] below; path counts
+                            orswot_add_device_files / _ops / _members)                       */
   CE_STATE_MVREG = 3,    /* MVReg<u64, Uuid>: op = mvreg::Op::Put{clock, val}                 */
   CE_STATE_PNCOUNTER = 4,/* PNCounter<Uuid> {p, n: GCounter}: op = pncounter::Op {dot, dir: Pos |
                             Neg}.  Every ce_core_* entry point that takes a GCounter core takes
@@ -622,6 +625,54 @@ int ce_core_gset_apply_members_device(ce_core *c, const uint64_t *d_members, uin
 int ce_core_gset_apply_members(ce_core *c, const uint64_t *members, uint64_t n, uint32_t per_file,
                                uint32_t flags, const uint8_t *nonces, ce_buf *files,
                                ce_buf *file_offs, uint32_t *n_files);
+/* ---- CE_STATE_ORSWOT: Add-op files written from a member column in HBM (Core::apply_ops,
+ * lib.rs:666-722, without the host).  The column is cut, in order, into n_ops = ceil(n / per_op)
+ * Add ops of per_op members (the last may be shorter), and the ops, in order, into
+ * F = ceil(n_ops / ops_per_file) ops vectors (the last may hold fewer).  Op j of the call is
+ * Add { dot: Dot { actor: local, counter: c0 + 1 + j }, members }, c0 = the committed clock's
+ * counter of the local actor at the call -- what derive_add_ctx would hand out one op after
+ * another, so every op is applied.  Each vector is one apply_ops(Vec<orswot::Op>) by the local
+ * actor and the effect equals ce_core_apply_ops_batch over the same F vectors: entries and clock
+ * updated, the deferred removals applied again, file i stored as ops/<local actor>/<v0 + i> when
+ * the core has storage, next_op_versions of the local actor raised by F.  Everything is sealed
+ * before anything is stored, folded or bumped; a failure once the fold has started leaves the core
+ * failing until ce_core_reset.
+ * File i = CURRENT_VERSION || Cryptor::encrypt(current_data_version || to_vec_named(Vec<Op>)):
+ * the Vec's fixarray or array16 header, then per op 81 a3 "Add" 82 a3 "dot" 82 a5 "actor" c4 10
+ * <16 bytes> a7 "counter" <counter> a7 "members" <fixarray or array16 header> <members>, every
+ * integer in its smallest unsigned form (1, 2, 3, 5 or 9 bytes) -- an op is 51 + w(counter) +
+ * h(count) + sum w(member) bytes.  Sealed under the latest key with nonce i (nonces: host, 24
+ * bytes a file; NULL: the OS RNG).  The files lie back to back in d_files (cap bytes), their F + 1
+ * offsets go to d_file_offs (room for max_files + 1), *n_files = F, *bytes = the files' total.
+ * Shapes: every file's worst-case clear text is one 4096-byte page,
+ *   16 + h(ops_per_file) + ops_per_file * (60 + h(per_op) + 9 * per_op) <= 4096   (h = 1 up to 15, else 3).
+ * per_op 0 means 1.  At per_op 1 (a dot per member) ops_per_file may be 1..58 and 0 means 28: the
+ * most whose worst case stays inside the 2048 bytes the readers' fused open decodes in LDS.  At
+ * per_op > 1 (add_all's shape) 0 means the most the rule allows; one op holds up to 446 members.
+ * n = 0: F = 0, d_file_offs[0] = 0, nothing else is written or bumped, CE_OK.
+ * Refused before anything on the core changes, no output touched: CE_ERR_INVALID_ARG -- another
+ * kind (MVReg too), a pair past the page rule, flags != 0, cap below ce_core_orswot_add_bound's
+ * bytes, n, n_ops or the clear-text bound reaching 2^32, c0 + n_ops passing 2^64 - 1;
+ * CE_ERR_NO_KEY.  Host traffic without storage: c0, *n_files and *bytes; no member and no file
+ * byte.  The column has been read on return.
+ * ce_core_path_count keys: orswot_add_device_files, orswot_add_device_ops,
+ * orswot_add_device_members.  Timing regions: orswot_add_sizes, orswot_add_encode,
+ * orswot_add_cols (the fold keeps its own).  Rm ops are not written here. ---- */
+/* worst-case outputs for a column of n members (9-byte counters and members); CE_ERR_INVALID_ARG:
+ * a pair past the page rule, or more than 2^32 - 1 files.  Any output may be NULL */
+int ce_core_orswot_add_bound(uint64_t n, uint32_t per_op, uint32_t ops_per_file,
+                             uint64_t *max_ops, uint32_t *max_files, uint64_t *max_bytes);
+int ce_core_orswot_add_members_device(ce_core *c, const uint64_t *d_members, uint64_t n,
+                                      uint32_t per_op, uint32_t ops_per_file, uint32_t flags /* 0 */,
+                                      const uint8_t *nonces /* host, max_files*24, or NULL */,
+                                      uint8_t *d_files, uint64_t cap,
+                                      uint64_t *d_file_offs /* max_files+1 */,
+                                      uint32_t *n_files, uint64_t *bytes);
+/* the same over a host column: upload, the device call, files and offsets back as ce_bufs (either
+ * may be NULL) */
+int ce_core_orswot_add_members(ce_core *c, const uint64_t *members, uint64_t n, uint32_t per_op,
+                               uint32_t ops_per_file, uint32_t flags, const uint8_t *nonces,
+                               ce_buf *files, ce_buf *file_offs, uint32_t *n_files);
 /* ---- CE_STATE_PNCOUNTER partitioned by op-file address (lib.rs:471-547).  ce_core_shard_stats,
  * ce_core_shard_window and ce_core_writer_versions take a PNCounter core as they are; the three
  * generic calls above keep refusing it (their dense buffers are one plane), and these take their
