@@ -74,8 +74,10 @@ EXPORTS = [
     "ce_ctx_prim_lww_reduce_keyed",
     "ce_core_gset_apply_bound", "ce_core_gset_apply_members_device", "ce_core_gset_apply_members",
     "ce_core_orswot_add_bound", "ce_core_orswot_add_members_device", "ce_core_orswot_add_members",
+    "ce_core_orswot_rm_members_device", "ce_core_orswot_rm_members",
 ]
 GSET_APPLY_NEW_ONLY = 1
+ORSWOT_RM_LIVE_ONLY = 1     # only the first occurrence of each live member is written
 GSET_FILE_MEMBERS = 453     # the most members a written op file holds (one 4096-byte page at 9 bytes each)
 
 
@@ -1180,6 +1182,42 @@ class Core:
             self.p, cp if len(col) else None, ctypes.c_uint64(len(col)), ctypes.c_uint32(per_op),
             ctypes.c_uint32(ops_per_file), ctypes.c_uint32(flags),
             _cbuf(b"".join(nonces)) if nonces is not None else None,
+            ctypes.byref(fb), ctypes.byref(fo), ctypes.byref(nf))
+        if rc:
+            return rc, None
+        blob, fofs = _take(fb), _take(fo)
+        o = struct.unpack("<%dQ" % (nf.value + 1), fofs)
+        return 0, [blob[o[i]:o[i + 1]] for i in range(nf.value)]
+
+    # ---- CE_STATE_ORSWOT: Rm-op files written from a member column (Core::apply_ops without the host) ----
+    def orswot_rm_members_device(self, d_members, n, d_files, cap, d_file_offs, ops_per_file=0, flags=0, nonces=None):
+        """One Rm op a member of the column d_members (device u64[n]), its clock the member's
+        entries in the committed state, the ops cut into files of ops_per_file ops (0: 16), sealed
+        into d_files (device, cap bytes) with their offsets in d_file_offs (device
+        u64[n_files + 1]); stored when the core has storage, folded, next_op_versions bumped once
+        a file.  d_files None with cap 0 is the sizing call: the exact figures, nothing written or
+        changed.  flags ORSWOT_RM_LIVE_ONLY: only the first occurrence of each live member.
+        nonces: one 24-byte nonce a file (None: the OS RNG).  Returns (rc, n_ops, n_files, bytes)."""
+        no, nf, nb = ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+        rc = lib().ce_core_orswot_rm_members_device(
+            self.p, ctypes.c_void_p(d_members) if d_members else None, ctypes.c_uint64(n),
+            ctypes.c_uint32(ops_per_file), ctypes.c_uint32(flags),
+            _cbuf(b"".join(nonces)) if nonces is not None else None,
+            ctypes.c_void_p(d_files) if d_files else None, ctypes.c_uint64(cap),
+            ctypes.c_void_p(d_file_offs) if d_file_offs else None, ctypes.byref(no), ctypes.byref(nf), ctypes.byref(nb))
+        return rc, no.value, nf.value, nb.value
+
+    def orswot_rm_members(self, members, ops_per_file=0, flags=0, nonces=None):
+        """orswot_rm_members_device over a host column (anything numpy reads as u64): returns
+        (rc, [op file bytes])."""
+        import numpy as np
+        import struct
+        col, cp = _np_ptr(members, np.uint64)
+        fb, fo = Buf(), Buf()
+        nf = ctypes.c_uint32(0)
+        rc = lib().ce_core_orswot_rm_members(
+            self.p, cp if len(col) else None, ctypes.c_uint64(len(col)), ctypes.c_uint32(ops_per_file),
+            ctypes.c_uint32(flags), _cbuf(b"".join(nonces)) if nonces is not None else None,
             ctypes.byref(fb), ctypes.byref(fo), ctypes.byref(nf))
         if rc:
             return rc, None

@@ -2303,6 +2303,44 @@ int ce_core_orswot_add_members(ce_core* c, const uint64_t* members, uint64_t n, 
   return CE_OK;
 }
 
+int ce_core_orswot_rm_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, uint32_t ops_per_file,
+                                     uint32_t flags, const uint8_t* nonces, uint8_t* d_files, uint64_t cap,
+                                     uint64_t* d_file_offs, uint64_t* n_ops, uint32_t* n_files, uint64_t* bytes) {
+  if (!c || (n && !d_members) || !n_ops || !n_files || !bytes) return CE_ERR_INVALID_ARG;
+  if ((d_files && !d_file_offs) || (!d_files && cap)) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  int rc = ds_rm_check(c, n, ops_per_file, flags);
+  if (rc) return rc;
+  return ds_rm_members_device(c, d_members, n, ops_per_file, flags, nonces, d_files, cap, d_file_offs, n_ops, n_files,
+                              bytes);
+}
+
+int ce_core_orswot_rm_members(ce_core* c, const uint64_t* members, uint64_t n, uint32_t ops_per_file, uint32_t flags,
+                              const uint8_t* nonces, ce_buf* files, ce_buf* file_offs, uint32_t* n_files) {
+  if (!c || (n && !members) || !n_files) return CE_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> g(c->ctx->mu);
+  (void)hipSetDevice(c->ctx->device);
+  int rc = ds_rm_check(c, n, ops_per_file, flags);
+  if (rc) return rc;
+  std::vector<uint8_t> out;
+  std::vector<uint64_t> fo;
+  uint32_t F = 0;
+  if ((rc = ds_rm_members_host(c, members, n, ops_per_file, flags, nonces, &out, &fo, &F))) return rc;
+  if (files) {
+    files->data = (uint8_t*)malloc(out.size() ? out.size() : 1);
+    std::memcpy(files->data, out.data(), out.size());
+    files->len = out.size();
+  }
+  if (file_offs) {
+    file_offs->data = (uint8_t*)malloc(fo.size() * 8);
+    std::memcpy(file_offs->data, fo.data(), fo.size() * 8);
+    file_offs->len = fo.size() * 8;
+  }
+  *n_files = F;
+  return CE_OK;
+}
+
 int ce_core_reset(ce_core* c) {
   if (!c) return CE_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> g(c->ctx->mu);

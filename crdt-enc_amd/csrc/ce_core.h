@@ -321,6 +321,17 @@ int ds_add_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, con
 // the same over a host column: the files and their n_files + 1 offsets come back to the host
 int ds_add_members_host(ce_core* c, const uint64_t* members, uint64_t n, const OwShape& sh, const uint8_t* nonces,
                         std::vector<uint8_t>* files, std::vector<uint64_t>* file_offs, uint32_t* n_files);
+// The Orswot Rm-op writer (ce_core_orswot_rm_members[_device]): one Rm op a member of the column,
+// its clock the member's entries in the committed state.  ds_rm_check: everything either form
+// refuses from its arguments alone.  ds_rm_members_device: d_files null is the sizing call (the
+// exact n_ops / n_files / bytes, nothing written or changed); else cap is checked against the
+// exact bytes behind the size passes, before the seal.
+int ds_rm_check(ce_core* c, uint64_t n, uint32_t ops_per_file, uint32_t flags);
+int ds_rm_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, uint32_t ops_per_file, uint32_t flags,
+                         const uint8_t* nonces, uint8_t* d_files, uint64_t cap, uint64_t* d_file_offs, uint64_t* n_ops,
+                         uint32_t* n_files, uint64_t* bytes);
+int ds_rm_members_host(ce_core* c, const uint64_t* members, uint64_t n, uint32_t ops_per_file, uint32_t flags,
+                       const uint8_t* nonces, std::vector<uint8_t>* out, std::vector<uint64_t>* fo, uint32_t* n_files);
 
 // GSet<u64> (ce_gset_host.cpp): the members live in a device hash set; next_op_versions, the
 // actor table and the storage plumbing are ce_core.cpp's, as for every kind

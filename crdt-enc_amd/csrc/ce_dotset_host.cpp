@@ -25,6 +25,7 @@
 #include "ce_dotset.h"
 #include "ce_dotset_codec.h"
 #include "ce_dotset_io.h"
+#include "ce_orswot_rm.h"
 #include "ce_orswot_write.h"
 
 namespace ce {
@@ -116,6 +117,12 @@ struct DsState {
   // olen | ooff (ops + 1 of each) and clen | xlen | coff | xoff (files + 1 of each); the host
   // twin's uploaded column, sealed files and offsets
   DevBuf ow_wr, ow_col, ow_files, ow_offs;
+  // the Rm-op writer (ds_rm_members_device): a word per member slot, all ones between calls
+  // (rm_first_clean; cleared for rm_first_slots of them); the per-position, per-op and per-file
+  // words; the gathered and sorted entries
+  DevBuf rm_first, rm_wr, rm_ent;
+  uint64_t rm_first_slots = 0;
+  bool rm_first_clean = false;
 };
 
 void ds_free(DsState* d) { delete d; }
@@ -2785,6 +2792,333 @@ int ds_add_members_host(ce_core* c, const uint64_t* members, uint64_t n, const O
   return CE_OK;
 }
 
+// actor UUIDs and UUID-order ranks by stable id, in HBM and on the host (kept: next_op_versions
+// and the clock are written in UUID order by walking the ranks -- no per-step sort), for the
+// actor table as it stands: rebuilt when ids were added since
+static int ensure_actor_ranks(ce_core* c, ce_ctx* x) {
+  DsState* d = c->ds;
+  hipStream_t s = x->stream;
+  hipError_t e;
+  const uint32_t na = (uint32_t)c->id_actor.size();
+  if (d->uuid_ids == na) return CE_OK;
+  std::vector<uint8_t> u(16ull * na + 16);
+  d->rank_id.resize(na);
+  d->id_rank.assign(na + 1, 0);
+  for (uint32_t i = 0; i < na; i++) {
+    std::memcpy(u.data() + 16ull * i, c->id_actor[i].data(), 16);
+    d->rank_id[i] = i;
+  }
+  std::sort(d->rank_id.begin(), d->rank_id.end(), [&](uint32_t a, uint32_t b) { return c->id_actor[a] < c->id_actor[b]; });
+  for (uint32_t i = 0; i < na; i++) d->id_rank[d->rank_id[i]] = i;
+  if ((e = d->uuid_of_id.reserve(u.size())) || (e = d->rank_of_id.reserve(4ull * d->id_rank.size())) ||
+      (e = d->id_of_rank.reserve(4ull * d->rank_id.size() + 64)) ||
+      (e = hipMemcpyAsync(d->uuid_of_id.p, u.data(), u.size(), hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(d->rank_of_id.p, d->id_rank.data(), 4ull * d->id_rank.size(), hipMemcpyHostToDevice, s)) ||
+      (na && (e = hipMemcpyAsync(d->id_of_rank.p, d->rank_id.data(), 4ull * na, hipMemcpyHostToDevice, s))) ||
+      (e = stream_wait(s)))
+    return x->hip_fail(e, "actor ranks");
+  d->uuid_ids = na;
+  return CE_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The Rm-op writer (ce_core_orswot_rm_members[_device]): Core::apply_ops (lib.rs:666-722) over a
+// member column in HBM, one Rm { clock: entries[m], members: [m] } a member with the clocks as
+// the committed tables hold them at the call; gathered, ordered, sized and encoded by
+// ce_orswot_rm.hip, sealed by device_seal into the caller's buffer, then stored, folded from
+// removal columns filled on the device and counted in next_op_versions.  d_files null: the sizing
+// call, which stops behind the size passes.
+// ---------------------------------------------------------------------------------------
+int ds_rm_check(ce_core* c, uint64_t n, uint32_t opf, uint32_t flags) {
+  ce_ctx* ctx = c->ctx;
+  if (c->kind != CE_STATE_ORSWOT) return ctx->fail(CE_ERR_INVALID_ARG, "orswot rm: not an Orswot core");
+  if (flags & ~(uint32_t)CE_ORSWOT_RM_LIVE_ONLY) return ctx->fail(CE_ERR_INVALID_ARG, "orswot rm: unknown flags");
+  if (opf > 65535) return ctx->fail(CE_ERR_INVALID_ARG, "orswot rm: ops_per_file above 65,535");
+  if (n >= (1ull << 32)) return ctx->fail(CE_ERR_INVALID_ARG, "orswot rm: column too large for 32-bit offsets");
+  if (!c->has_key) return ctx->fail(CE_ERR_NO_KEY, "no latest key");
+  return CE_OK;
+}
+
+int ds_rm_members_device(ce_core* c, const uint64_t* d_members, uint64_t n64, uint32_t opf, uint32_t flags,
+                         const uint8_t* nonces, uint8_t* d_files, uint64_t cap, uint64_t* d_file_offs, uint64_t* n_ops_out,
+                         uint32_t* n_files, uint64_t* bytes) {
+  ce_ctx* ctx = c->ctx;
+  DsState* d = c->ds;
+  hipStream_t s = ctx->stream;
+  hipError_t e;
+  int rc;
+  const bool sizing = d_files == nullptr;
+  if (opf == 0) opf = 16;
+  if ((rc = ds_settle(c))) return rc;
+  const uint32_t n = (uint32_t)n64;
+  auto nothing = [&]() -> int {  // no op to write: the one offset, no file, no version
+    if (!sizing && ((e = hipMemsetAsync(d_file_offs, 0, 8, s)) || (e = stream_wait(s)))) return ctx->hip_fail(e, "orswot rm");
+    *n_ops_out = 0;
+    *n_files = 0;
+    *bytes = 0;
+    return CE_OK;
+  };
+  if (n == 0) return nothing();
+  const uint64_t slots = (uint64_t)d->mcap_s + d->pcap + 1;
+  if (slots >= kRmNoHandle) return ctx->fail(CE_ERR_INVALID_ARG, "orswot rm: member table too large for 32-bit handles");
+  if ((rc = ensure_actor_ranks(c, ctx))) return rc;
+  const uint32_t na = (uint32_t)c->id_actor.size();
+  // words: tot (u64 x 4) | offs (u64 x (n + 1)) | 14 u32 columns of n + 1
+  const uint64_t n1 = (uint64_t)n + 1;
+  size_t cb = 0;
+  if ((e = d->rm_wr.reserve(8ull * kRmTotN + 8ull * n1 + 4ull * 14 * n1 + 64)) ||
+      (e = ds_excl_sum_u32(nullptr, cb, nullptr, nullptr, n + 1, s)) || (e = d->cub_tmp.reserve(cb + 256)))
+    return ctx->hip_fail(e, "orswot rm reserve");
+  {  // the marks: all ones between calls, cleared behind the scans that read them
+    void* was = d->rm_first.p;
+    if ((e = d->rm_first.reserve(slots * 4 + 64))) return ctx->hip_fail(e, "orswot rm reserve");
+    if (was != d->rm_first.p || d->rm_first_slots < slots || !d->rm_first_clean) {
+      if ((e = hipMemsetAsync(d->rm_first.p, 0xff, slots * 4, s))) return ctx->hip_fail(e, "orswot rm marks");
+      d->rm_first_slots = slots;
+    }
+  }
+  RmArgs a{};
+  a.t = tables(d);
+  a.members = reinterpret_cast<const unsigned long long*>(d_members);
+  a.n = n;
+  a.live_only = flags & CE_ORSWOT_RM_LIVE_ONLY ? 1u : 0u;
+  a.first = d->rm_first.as<uint32_t>();
+  a.tot = d->rm_wr.as<unsigned long long>();
+  a.offs = a.tot + kRmTotN;
+  uint32_t* w = reinterpret_cast<uint32_t*>(a.offs + n1);
+  a.hnd = w;
+  a.cnt = w + n1;
+  a.ebytes = w + 2 * n1;
+  a.rep = w + 3 * n1;
+  a.keep = w + 4 * n1;
+  uint32_t* kpos = w + 5 * n1;
+  uint32_t* ebeg = w + 6 * n1;
+  a.op_pos = w + 7 * n1;
+  a.olen = w + 8 * n1;
+  uint32_t* ooff = w + 9 * n1;
+  a.clen = w + 10 * n1;
+  a.xlen = w + 11 * n1;
+  uint32_t* coff = w + 12 * n1;
+  uint32_t* xoff = w + 13 * n1;
+  a.kpos = kpos;
+  a.ebeg = ebeg;
+  a.ooff = ooff;
+  a.coff = coff;
+  a.xoff = xoff;
+  a.rank_of_id = d->rank_of_id.as<uint32_t>();
+  a.id_of_rank = d->id_of_rank.as<uint32_t>();
+  a.uuid_of_id = d->uuid_of_id.as<uint8_t>();
+  a.rank_bits = bits_for(na);
+  a.n_ids = na;
+  a.opf = opf;
+  cb = d->cub_tmp.cap;
+  // 1) representatives and the first scan of the pair table: counts and bytes per representative
+  d->rm_first_clean = false;
+  int t = ctx->tbegin("orswot_rm_clocks");
+  unsigned long long tot[kRmTotN] = {0, 0, 0, 0};
+  if ((e = hipMemsetAsync(a.tot, 0, 8ull * kRmTotN, s)) || (e = hipMemsetAsync(a.cnt, 0, 8ull * n1, s)) ||
+      (e = launch_rm_mark(s, a)) || (e = launch_rm_count(s, a)) || (e = launch_rm_keep(s, a)) ||
+      (sizing && (e = launch_rm_unmark(s, a))) ||
+      (e = hipMemcpyAsync(tot, a.tot, 8ull * kRmTotN, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+    return ctx->hip_fail(e, "orswot rm clocks");
+  ctx->tend(t);
+  if (sizing) d->rm_first_clean = true;
+  auto leave = [&](int code, const char* msg) -> int {  // a refusal behind the marks: they are cleared first
+    if (!d->rm_first_clean && !(e = launch_rm_unmark(s, a)) && !(e = stream_wait(s))) d->rm_first_clean = true;
+    return ctx->fail(code, msg);
+  };
+  const uint64_t E = tot[kRmTotEntries], n_ops64 = tot[kRmTotOps];
+  const uint64_t F64 = (n_ops64 + opf - 1) / opf;
+  if (n_ops64 > n || E > kSortMaxItems || tot[kRmTotOpEntries] >= (1ull << 32) ||
+      rm_clear_bound(n_ops64, tot[kRmTotOpEntries], F64) + 65536 >= (1ull << 32))
+    return leave(CE_ERR_INVALID_ARG, "orswot rm: the clocks' entries pass 32-bit offsets");
+  const uint32_t n_ops = (uint32_t)n_ops64, F = (uint32_t)F64;
+  if (n_ops == 0) {
+    if (!d->rm_first_clean) {
+      if ((e = launch_rm_unmark(s, a))) return ctx->hip_fail(e, "orswot rm marks");
+      d->rm_first_clean = true;
+    }
+    return nothing();
+  }
+  a.n_ops = n_ops;
+  a.n_files = F;
+  a.n_ent = (uint32_t)E;
+  // 2) sizes: op lengths, file lengths and their sealed extras, from the first scan alone
+  t = ctx->tbegin("orswot_rm_sizes");
+  if ((e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.keep, kpos, n + 1, s)) || (e = launch_rm_scatter(s, a)) ||
+      (e = launch_rm_op_sizes(s, a)) || (e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.olen, ooff, n_ops + 1, s)) ||
+      (e = launch_rm_file_sizes(s, a)) || (e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.clen, coff, F + 1, s)) ||
+      (e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.xlen, xoff, F + 1, s)))
+    return ctx->hip_fail(e, "orswot rm sizes");
+  ctx->tend(t);
+  uint32_t ends[2] = {0, 0};
+  if ((e = hipMemcpyAsync(&ends[0], coff + F, 4, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(&ends[1], xoff + F, 4, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+    return ctx->hip_fail(e, "orswot rm sizes");
+  const uint64_t U = ends[0], total = U + (uint64_t)F * kOwSealBase + ends[1];
+  if (sizing) {
+    *n_ops_out = n_ops;
+    *n_files = F;
+    *bytes = total;
+    return CE_OK;
+  }
+  if (cap < total) return leave(CE_ERR_INVALID_ARG, "orswot rm: d_files below the sizing call's bytes");
+  // 3) the second scan, the sort and the sorted entry columns
+  size_t sb = 0;
+  const int key_bits = bits_for(n) + a.rank_bits;
+  if ((e = d->rm_ent.reserve(44ull * E + 256)) ||
+      (E && (e = sort_pairs_u64(nullptr, sb, nullptr, nullptr, nullptr, nullptr, a.n_ent, key_bits, s))) ||
+      (e = d->cub_tmp.reserve(std::max(sb, cb) + 256)) || (e = ctx->blob.reserve(U + 64)) ||
+      (e = ctx->nonces.reserve(24ull * F)) || (e = ctx->outer_ver.reserve(64)))
+    return ctx->hip_fail(e, "orswot rm reserve");
+  cb = sb = d->cub_tmp.cap;
+  a.key = d->rm_ent.as<unsigned long long>();
+  a.ctr = a.key + E;
+  unsigned long long* skey = a.ctr + E;
+  a.s_ctr = skey + E;
+  a.idx = reinterpret_cast<uint32_t*>(a.s_ctr + E);
+  uint32_t* sidx = a.idx + E;
+  a.s_actor = sidx + E;
+  a.skey = skey;
+  a.sidx = sidx;
+  std::vector<uint8_t> nb;
+  if (!nonces) {
+    nb.resize(24ull * F);
+    os_random(nb.data(), nb.size());
+    nonces = nb.data();
+  }
+  std::memcpy(a.dv, c->current_data_version.data(), 16);
+  {  // an op up to its clock's map header, then a7 "members" 91 (to_vec_named: structs as maps, the variant by name)
+    Wr hw;
+    hw.map(1);
+    hw.str("Rm");
+    hw.map(2);
+    hw.str("clock");
+    hw.map(1);
+    hw.str("dots");
+    if (hw.b.size() != kRmHeadBytes) return leave(CE_ERR_DEVICE, "orswot rm: op head");
+    hw.str("members");
+    hw.arr(1);
+    if (hw.b.size() != kRmFixedBytes) return leave(CE_ERR_DEVICE, "orswot rm: op head");
+    std::memcpy(a.head, hw.b.data(), kRmFixedBytes);
+  }
+  a.clear = ctx->blob.as<uint8_t>();
+  a.file_offs = reinterpret_cast<unsigned long long*>(d_file_offs);
+  if ((e = hipMemcpyAsync(ctx->nonces.p, nonces, 24ull * F, hipMemcpyHostToDevice, s)) ||
+      (e = hipMemcpyAsync(ctx->outer_ver.p, kCoreVersion, 16, hipMemcpyHostToDevice, s)))
+    return ctx->hip_fail(e, "orswot rm upload");
+  t = ctx->tbegin("orswot_rm_clocks");
+  if ((e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.cnt, ebeg, n + 1, s)) || (e = launch_rm_gather(s, a)) ||
+      (e = launch_rm_unmark(s, a)) ||
+      (E && (e = sort_pairs_u64(d->cub_tmp.p, sb, a.key, skey, a.idx, sidx, a.n_ent, key_bits, s))) ||
+      (e = launch_rm_entries(s, a)))
+    return ctx->hip_fail(e, "orswot rm clocks");
+  ctx->tend(t);
+  d->rm_first_clean = true;
+  // 4) the clear texts, straight into the seal's input blob
+  t = ctx->tbegin("orswot_rm_encode");
+  if ((e = launch_rm_encode(s, a, test_grid_cap()))) return ctx->hip_fail(e, "orswot rm encode");
+  ctx->tend(t);
+  // file i = CURRENT_VERSION || Cryptor::encrypt(clear_i) (lib.rs:682-695), straight into d_files
+  if ((rc = device_seal(ctx, a.clear, reinterpret_cast<const uint64_t*>(a.offs), F, U, ctx->outer_ver.as<uint8_t>(),
+                        ctx->nonces.as<uint8_t>(), d_files, d_file_offs, key_of(c))))
+    return rc;
+  uint64_t sealed = 0, gathered = 0;
+  if ((e = hipMemcpyAsync(&sealed, d_file_offs + F, 8, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(&gathered, a.tot + kRmTotGather, 8, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+    return ctx->hip_fail(e, "orswot rm");
+  if (sealed != total || gathered != E) return ctx->fail(CE_ERR_DEVICE, "orswot rm: the two scans disagree");
+  // everything is sealed: stored, folded and bumped from here on
+  uint32_t slot;
+  if ((rc = insert_actor(c, c->local_actor, &slot))) return rc;
+  const uint64_t v0 = c->nov[slot];  // next_op_versions.get(actor) (lib.rs:703)
+  if (c->storage) {
+    std::vector<uint8_t> out(total);
+    std::vector<uint64_t> fo(F + 1);
+    if ((e = hipMemcpyAsync(out.data(), d_files, total, hipMemcpyDeviceToHost, s)) ||
+        (e = hipMemcpyAsync(fo.data(), d_file_offs, 8ull * (F + 1), hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+      return ctx->hip_fail(e, "orswot rm download");
+    for (uint32_t i = 0; i < F; i++)
+      if ((rc = storage_store_op(c->storage, c->local_actor, v0 + i, out.data() + fo[i], fo[i + 1] - fo[i])))
+        return ctx->fail(rc, "failed writing ops file");
+  }
+  // state.apply(op) for op in ops (lib.rs:710-712): the fold's removal columns filled from the
+  // sorted entries in HBM, one removal a position of the column.  Only a member's first position
+  // carries its clock: a second identical Rm is idempotent (it removes dots the first has
+  // removed), and under the flag the positions left out carry the empty clock.  No adds, so the
+  // add path's flags play no part.
+  Counts cnts;
+  cnts.v[kCntRm] = n;
+  cnts.v[kCntRmC] = E;
+  cnts.v[kCntRmM] = n;
+  if ((rc = table_upload(c)) || (rc = ensure_clock(c)) || (rc = reserve_ops(c, cnts))) return rc;
+  DsOps o = ops_view(d);
+  RmCols rc_{};
+  rc_.members = a.members;
+  rc_.n = n;
+  rc_.n_ent = a.n_ent;
+  rc_.ebeg = ebeg;
+  rc_.s_actor = a.s_actor;
+  rc_.s_ctr = a.s_ctr;
+  rc_.add_mbeg = o.add_mbeg;
+  rc_.rm_cbeg = o.rm_cbeg;
+  rc_.rm_mbeg = o.rm_mbeg;
+  rc_.rmc_actor = o.rmc_actor;
+  rc_.rmc_ctr = o.rmc_ctr;
+  rc_.rm_mem = o.rm_mem;
+  t = ctx->tbegin("orswot_rm_cols");
+  if ((e = launch_rm_cols(s, rc_))) return ctx->hip_fail(e, "orswot rm columns");
+  ctx->tend(t);
+  d->adds_mono = false;
+  d->adds_mono_n = 0;
+  rc = orswot_fold(c, cnts, E, false);
+  // the closing counts, and the column is the caller's again; a failure from the fold on leaves
+  // tables that no longer describe a state
+  if (!rc) rc = ds_settle(c);
+  if (rc) {
+    d->poisoned = true;
+    return rc;
+  }
+  slot = c->slot_of.at(c->local_actor);
+  c->nov[slot] = v0 + F;  // next_op_versions.inc(actor), once a file (lib.rs:714-715)
+  c->path_counts["orswot_rm_device_files"] += F;
+  c->path_counts["orswot_rm_device_ops"] += n_ops;
+  c->path_counts["orswot_rm_device_entries"] += tot[kRmTotOpEntries];
+  *n_ops_out = n_ops;
+  *n_files = F;
+  *bytes = total;
+  return table_upload(c);
+}
+
+int ds_rm_members_host(ce_core* c, const uint64_t* members, uint64_t n, uint32_t opf, uint32_t flags, const uint8_t* nonces,
+                       std::vector<uint8_t>* out, std::vector<uint64_t>* fo, uint32_t* n_files) {
+  ce_ctx* ctx = c->ctx;
+  DsState* d = c->ds;
+  hipStream_t s = ctx->stream;
+  hipError_t e;
+  int rc;
+  if ((e = d->ow_col.reserve(n * 8 + 64)) ||
+      (n && (e = hipMemcpyAsync(d->ow_col.p, members, n * 8, hipMemcpyHostToDevice, s))))
+    return ctx->hip_fail(e, "orswot rm upload");
+  uint32_t F = 0;
+  uint64_t total = 0, n_ops = 0;
+  // the sizing call reserves; the state does not change between the two
+  if ((rc = ds_rm_members_device(c, d->ow_col.as<uint64_t>(), n, opf, flags, nullptr, nullptr, 0, nullptr, &n_ops, &F, &total)))
+    return rc;
+  if ((e = d->ow_files.reserve(total + 64)) || (e = d->ow_offs.reserve(8ull * (F + 1ull) + 64)))
+    return ctx->hip_fail(e, "orswot rm reserve");
+  if ((rc = ds_rm_members_device(c, d->ow_col.as<uint64_t>(), n, opf, flags, nonces, d->ow_files.as<uint8_t>(), total + 64,
+                                 d->ow_offs.as<uint64_t>(), &n_ops, &F, &total)))
+    return rc;
+  out->resize(total);
+  fo->resize(F + 1);
+  if ((total && (e = hipMemcpyAsync(out->data(), d->ow_files.p, total, hipMemcpyDeviceToHost, s))) ||
+      (e = hipMemcpyAsync(fo->data(), d->ow_offs.p, 8ull * (F + 1), hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+    return ctx->hip_fail(e, "orswot rm download");
+  *n_files = F;
+  return CE_OK;
+}
+
 // Compaction of an Orswot state without bringing the entries to the host: the clear text
 // (prefix16 || to_vec_named(StateWrapper), the same bytes as ds_serialize) is written into
 // x->blob by the device writer (ce_dotset_io.hip) around a host-built head (next_op_versions,
@@ -2816,25 +3150,7 @@ static int ds_serialize_dev(ce_core* c, ce_ctx* x, const uint8_t* outer, const u
   // written in UUID order by walking the ranks -- no per-step sort)
   auto cph = std::make_unique<HostPhase>("  cd: actor order");
   const uint32_t na = (uint32_t)c->id_actor.size();
-  if (d->uuid_ids != na) {
-    std::vector<uint8_t> u(16ull * na + 16);
-    d->rank_id.resize(na);
-    d->id_rank.assign(na + 1, 0);
-    for (uint32_t i = 0; i < na; i++) {
-      std::memcpy(u.data() + 16ull * i, c->id_actor[i].data(), 16);
-      d->rank_id[i] = i;
-    }
-    std::sort(d->rank_id.begin(), d->rank_id.end(), [&](uint32_t a, uint32_t b) { return c->id_actor[a] < c->id_actor[b]; });
-    for (uint32_t i = 0; i < na; i++) d->id_rank[d->rank_id[i]] = i;
-    if ((e = d->uuid_of_id.reserve(u.size())) || (e = d->rank_of_id.reserve(4ull * d->id_rank.size())) ||
-        (e = d->id_of_rank.reserve(4ull * d->rank_id.size() + 64)) ||
-        (e = hipMemcpyAsync(d->uuid_of_id.p, u.data(), u.size(), hipMemcpyHostToDevice, s)) ||
-        (e = hipMemcpyAsync(d->rank_of_id.p, d->id_rank.data(), 4ull * d->id_rank.size(), hipMemcpyHostToDevice, s)) ||
-        (na && (e = hipMemcpyAsync(d->id_of_rank.p, d->rank_id.data(), 4ull * na, hipMemcpyHostToDevice, s))) ||
-        (e = stream_wait(s)))
-      return x->hip_fail(e, "actor ranks");
-    d->uuid_ids = na;
-  }
+  if ((rc = ensure_actor_ranks(c, x))) return rc;
   // head: [prefix16] map(2) "next_op_versions" nov "state" map(3) "clock" clock "entries"
   cph = std::make_unique<HostPhase>("  cd: nov");
   std::vector<uint64_t> by_rank(na, 0);

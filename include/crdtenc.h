@@ -657,7 +657,7 @@ int ce_core_gset_apply_members(ce_core *c, const uint64_t *members, uint64_t n, 
  * byte.  The column has been read on return.
  * ce_core_path_count keys: orswot_add_device_files, orswot_add_device_ops,
  * orswot_add_device_members.  Timing regions: orswot_add_sizes, orswot_add_encode,
- * orswot_add_cols (the fold keeps its own).  Rm ops are not written here. ---- */
+ * orswot_add_cols (the fold keeps its own).  Rm ops: ce_core_orswot_rm_members[_device] below. ---- */
 /* worst-case outputs for a column of n members (9-byte counters and members); CE_ERR_INVALID_ARG:
  * a pair past the page rule, or more than 2^32 - 1 files.  Any output may be NULL */
 int ce_core_orswot_add_bound(uint64_t n, uint32_t per_op, uint32_t ops_per_file,
@@ -673,6 +673,57 @@ int ce_core_orswot_add_members_device(ce_core *c, const uint64_t *d_members, uin
 int ce_core_orswot_add_members(ce_core *c, const uint64_t *members, uint64_t n, uint32_t per_op,
                                uint32_t ops_per_file, uint32_t flags, const uint8_t *nonces,
                                ce_buf *files, ce_buf *file_offs, uint32_t *n_files);
+/* ---- CE_STATE_ORSWOT: Rm-op files written from a member column in HBM (Core::apply_ops,
+ * lib.rs:666-722, without the host).  One op a member, Orswot::rm(member, ctx) with
+ * ctx = contains(member).derive_rm_ctx():
+ *   Rm { clock: entries[m] as read from the COMMITTED state at the call, members: [m] }.
+ * Every clock is read before anything changes: op i's clock does not see ops 0..i-1 of the call.
+ * A member that is absent, or whose dots are all removed, gets the empty clock: a no-op that is
+ * still written.  A member that occurs twice gets the same op twice.  An entry clock is <= the
+ * set's clock, so no op of this writer is deferred.  The ops are cut, in order, into
+ * F = ceil(n_ops / ops_per_file) vectors (ops_per_file 0 means 16; 1..65,535); each vector is one
+ * apply_ops by the local actor (lib.rs:666-722) and the effect equals ce_core_apply_ops_batch over
+ * the same F vectors: file i stored as ops/<local actor>/<v0 + i> when the core has storage,
+ * next_op_versions of the local actor raised by F, the set's clock unchanged.  Everything is sealed
+ * before anything is stored, folded or bumped; a failure once the fold has started leaves the core
+ * failing until ce_core_reset.
+ * File i = CURRENT_VERSION || Cryptor::encrypt(current_data_version || to_vec_named(Vec<Op>)):
+ * the Vec's fixarray or array16 header, then per op 81 a2 "Rm" 82 a5 "clock" 81 a4 "dots"
+ * <map header of k> k x (c4 10 <16 UUID bytes> <counter>) a7 "members" 91 <member>, the entries
+ * ascending by UUID bytes, every integer in its smallest unsigned form -- an op is
+ * 26 + hm(k) + sum (18 + w(counter)) + w(member) bytes (hm = 1 up to 15 entries, 3 up to 65,535,
+ * else 5).  A file may pass one page: an op's length depends on the state.
+ * CE_ORSWOT_RM_LIVE_ONLY: only the first occurrence of each member that is live is written, in
+ * the column's order; *n_ops = the ops written.
+ * Sizing call (lib.rs:666-722 has no counterpart; it takes the place of a _bound function, since
+ * the worst case cannot be bounded without the state): d_files == NULL and cap == 0 -- *n_ops,
+ * *n_files and *bytes are the exact figures for the committed state, nothing is written, sealed,
+ * stored, folded or bumped, nonces and d_file_offs are ignored, CE_OK.
+ * n = 0, or nothing live under the flag: F = 0, d_file_offs[0] = 0, nothing else is written or
+ * bumped, CE_OK.
+ * Refused before anything on the core changes, no output touched: CE_ERR_INVALID_ARG -- another
+ * kind (MVReg too), unknown flag bits, ops_per_file > 65,535, n >= 2^32, 2^30 or more entries in
+ * the clocks or a clear-text bound from their count reaching 2^32, a non-NULL d_files with cap
+ * below the exact bytes (checked behind the size passes, before the seal); CE_ERR_NO_KEY.
+ * Host traffic without storage: the entry counts, the size totals, *n_ops, *n_files, *bytes, the
+ * nonces and the outer version going up, the fold's closing counts; no member, no clock entry and
+ * no file byte.  The column is read-only and has been read on return.
+ * ce_core_path_count keys: orswot_rm_device_files, orswot_rm_device_ops,
+ * orswot_rm_device_entries.  Timing regions: orswot_rm_clocks, orswot_rm_sizes, orswot_rm_encode,
+ * orswot_rm_cols (the seal and the fold keep theirs). ---- */
+#define CE_ORSWOT_RM_LIVE_ONLY 1u
+/* Core::apply_ops, lib.rs:666-722 */
+int ce_core_orswot_rm_members_device(ce_core *c, const uint64_t *d_members, uint64_t n,
+                                     uint32_t ops_per_file, uint32_t flags,
+                                     const uint8_t *nonces /* host, 24 * ceil(n/opf), or NULL */,
+                                     uint8_t *d_files, uint64_t cap,
+                                     uint64_t *d_file_offs /* ceil(n/opf) + 1 */,
+                                     uint64_t *n_ops, uint32_t *n_files, uint64_t *bytes);
+/* the same over a host column (lib.rs:666-722): upload, the device call (sizing first, to
+ * reserve), files and offsets back as ce_bufs (either may be NULL) */
+int ce_core_orswot_rm_members(ce_core *c, const uint64_t *members, uint64_t n, uint32_t ops_per_file,
+                              uint32_t flags, const uint8_t *nonces, ce_buf *files,
+                              ce_buf *file_offs, uint32_t *n_files);
 /* ---- CE_STATE_PNCOUNTER partitioned by op-file address (lib.rs:471-547).  ce_core_shard_stats,
  * ce_core_shard_window and ce_core_writer_versions take a PNCounter core as they are; the three
  * generic calls above keep refusing it (their dense buffers are one plane), and these take their
