@@ -1710,6 +1710,16 @@ int id_dots(ce_core* c, Dots d, IdDots* out) {
   return CE_OK;
 }
 
+// a deferred removal's clock as a state file holds it -> without its zero counters: a zero
+// counter is no dot (VClock::apply stores only counters above the current one, so no writer
+// built on crdts produces one), and a key that kept it would be written back with it
+Dots without_zero_dots(const Dots& d) {
+  Dots o;
+  for (auto& x : d)
+    if (x.second) o.push_back(x);
+  return o;
+}
+
 struct OtherCols {  // the other state's (member, actor id, value) columns in HBM
   const unsigned long long* member;
   const uint32_t* actor;
@@ -1761,7 +1771,7 @@ int orswot_merge_one(ce_core* c, const HostState& hs) {
   std::vector<std::pair<IdDots, std::vector<uint64_t>>> od;
   for (auto& x : hs.deferred) {
     IdDots k;
-    if ((rc = id_dots(c, x.first, &k))) return rc;
+    if ((rc = id_dots(c, without_zero_dots(x.first), &k))) return rc;
     od.push_back({k, x.second});
   }
   if ((rc = table_upload(c)) || (rc = ensure_clock(c)) || (rc = ensure_pairs(c, mem.size()))) return rc;
@@ -2340,7 +2350,7 @@ int ds_merge_states_device(ce_core* c, const uint8_t* out, const std::vector<uin
         x.od.clear();
         for (auto& y : x.hs.deferred) {
           IdDots k;
-          if ((rc = id_dots(c, y.first, &k))) return rc;
+          if ((rc = id_dots(c, without_zero_dots(y.first), &k))) return rc;
           x.od.push_back({k, y.second});
         }
         dev4.push_back(i);
@@ -3215,6 +3225,7 @@ static int ds_serialize_dev(ce_core* c, ce_ctx* x, const uint8_t* outer, const u
   sc.k64b = d->ser[16].as<unsigned long long>();
   const int t = x->tbegin("ds_serialize");
   if ((e = launch_orswot_ser_sort(s, sc, nl))) return x->hip_fail(e, "ds serialize");
+  if (nl) c->path_counts[sc.scan_form ? "ser_entries_scan_form" : "ser_entries_tile_form"]++;
   const unsigned long long* ck = d->h_clock.as<unsigned long long>();
   cph = std::make_unique<HostPhase>("  cd: head + tail bytes");
   Dots clock;

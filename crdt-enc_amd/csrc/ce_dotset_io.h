@@ -52,6 +52,7 @@ struct OrswotSerScratch {
   uint32_t* sort_state;
   uint32_t* sort_gen;                    // sorts so far (host): the state's histogram parity
   unsigned long long *k64b, *v64a, *v64b;
+  bool scan_form = false;                // out: the entry bookkeeping took the head / scan / seg / len / scan form
 };
 
 // the serializer's LSD radix sort (ce_ser_sort.hip): pairs (member_in, actor_in, value_in) in

@@ -808,7 +808,10 @@ hipError_t launch_orswot_ser_sort(hipStream_t s, OrswotSerScratch& sc, uint32_t 
                        sc.actor_sorted, sc.value_sorted, n);
   }
   const uint32_t nt = (n + kSerTile - 1) / kSerTile;
-  if (n && nt <= 4096 && 8ull * nt <= sc.tmp_bytes) {
+  // CE_SER_SCAN_FORM=1: the head / scan / seg / len / scan form below at any n
+  const bool scan_form = getenv("CE_SER_SCAN_FORM") != nullptr;  // (the tests flip it)
+  sc.scan_form = false;
+  if (n && !scan_form && nt <= 4096 && 8ull * nt <= sc.tmp_bytes) {
     // (an apply block sums the tile totals before it: up to 4096 tiles, 8M pairs)
     uint32_t* ts = static_cast<uint32_t*>(sc.tmp);
     hipLaunchKernelGGL(k_ser_head_tiles, dim3(nt), dim3(kB), 0, s, sc.member_sorted, n, ts);
@@ -818,6 +821,7 @@ hipError_t launch_orswot_ser_sort(hipStream_t s, OrswotSerScratch& sc, uint32_t 
     hipLaunchKernelGGL(k_ser_len_apply, dim3(nt), dim3(kB), 0, s, sc.member_sorted, sc.value_sorted, sc.head, sc.hrank,
                        sc.seg, n, ts + nt, sc.len, sc.pos);
   } else if (n) {
+    sc.scan_form = true;
     size_t tb = sc.tmp_bytes;
     hipLaunchKernelGGL(k_ser_head, dim3(nblk(n)), dim3(kB), 0, s, sc.member_sorted, sc.head, n);
     tb = sc.tmp_bytes;
