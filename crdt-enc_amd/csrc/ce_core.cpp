@@ -1761,9 +1761,7 @@ int ce_core_state_bytes(ce_core* c, ce_buf* out) {
   std::vector<uint8_t> b;
   int rc = serialize_state(c, &b);
   if (rc) return rc;
-  out->data = (uint8_t*)malloc(b.size() ? b.size() : 1);
-  std::memcpy(out->data, b.data(), b.size());
-  out->len = b.size();
+  fill_buf(out, b.data(), b.size());
   return CE_OK;
 }
 
@@ -1890,9 +1888,7 @@ int ce_core_compact_ops_device(ce_core* c, const uint8_t* d_blob, const uint64_t
   int rc = compact_ops_device_impl(c, d_blob, d_offs, n, blob_len, actors, m, d_file_actor, d_file_version,
                                    nonce, &p, &len, name_out);
   if (rc) return rc;
-  file->data = (uint8_t*)malloc(len ? len : 1);
-  std::memcpy(file->data, p, len);
-  file->len = len;
+  fill_buf(file, p, len);
   return CE_OK;
 }
 
@@ -1998,9 +1994,7 @@ int ce_core_compact_to_buffer(ce_core* c, const uint8_t* nonce, ce_buf* file, ch
     sha3_256(f.data(), f.size(), h);
     std::snprintf(name_out, 64, "%s", base32_nopad(h, 32).c_str());
   }
-  file->data = (uint8_t*)malloc(f.size() ? f.size() : 1);
-  std::memcpy(file->data, f.data(), f.size());
-  file->len = f.size();
+  fill_buf(file, f.data(), f.size());
   return CE_OK;
 }
 
@@ -2239,16 +2233,7 @@ int ce_core_apply_ops_batch(ce_core* c, const uint8_t* ops, const uint64_t* offs
     s = c->slot_of.at(c->local_actor);  // a growth inside the apply moved the local actor's slot
     c->nov[s] = v0 + i + 1;
   }
-  if (files) {
-    files->data = (uint8_t*)malloc(out.size() ? out.size() : 1);
-    std::memcpy(files->data, out.data(), out.size());
-    files->len = out.size();
-  }
-  if (file_offs) {
-    file_offs->data = (uint8_t*)malloc((n + 1) * 8ull);
-    std::memcpy(file_offs->data, foffs.data(), (n + 1) * 8ull);
-    file_offs->len = (n + 1) * 8ull;
-  }
+  fill_files(files, file_offs, out, foffs);
   return table_upload(c);
 }
 
@@ -2289,16 +2274,7 @@ int ce_core_orswot_add_members(ce_core* c, const uint64_t* members, uint64_t n, 
   std::vector<uint64_t> fo;
   uint32_t F = 0;
   if ((rc = ds_add_members_host(c, members, n, sh, nonces, &out, &fo, &F))) return rc;
-  if (files) {
-    files->data = (uint8_t*)malloc(out.size() ? out.size() : 1);
-    std::memcpy(files->data, out.data(), out.size());
-    files->len = out.size();
-  }
-  if (file_offs) {
-    file_offs->data = (uint8_t*)malloc(fo.size() * 8);
-    std::memcpy(file_offs->data, fo.data(), fo.size() * 8);
-    file_offs->len = fo.size() * 8;
-  }
+  fill_files(files, file_offs, out, fo);
   *n_files = F;
   return CE_OK;
 }
@@ -2327,16 +2303,7 @@ int ce_core_orswot_rm_members(ce_core* c, const uint64_t* members, uint64_t n, u
   std::vector<uint64_t> fo;
   uint32_t F = 0;
   if ((rc = ds_rm_members_host(c, members, n, ops_per_file, flags, nonces, &out, &fo, &F))) return rc;
-  if (files) {
-    files->data = (uint8_t*)malloc(out.size() ? out.size() : 1);
-    std::memcpy(files->data, out.data(), out.size());
-    files->len = out.size();
-  }
-  if (file_offs) {
-    file_offs->data = (uint8_t*)malloc(fo.size() * 8);
-    std::memcpy(file_offs->data, fo.data(), fo.size() * 8);
-    file_offs->len = fo.size() * 8;
-  }
+  fill_files(files, file_offs, out, fo);
   *n_files = F;
   return CE_OK;
 }
@@ -2540,12 +2507,6 @@ static bool has_counter(int kind) { return kind == CE_STATE_GCOUNTER || kind == 
 static bool has_clock(int kind, int which) {
   return kind != CE_STATE_GSET && kind != CE_STATE_LWWREG &&
          (which == 0 || (which == 1 && kind == CE_STATE_PNCOUNTER));
-}
-
-static void fill_buf(ce_buf* out, const void* p, size_t n) {
-  out->data = (uint8_t*)malloc(n ? n : 1);
-  if (n) std::memcpy(out->data, p, n);
-  out->len = n;
 }
 
 // (uuid16, u64 LE counter) entries ascending by UUID bytes

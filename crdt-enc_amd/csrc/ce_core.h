@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ce_internal.h"
+#include "ce_opfile.h"
 
 namespace ce {
 int storage_load_ops_vec(ce_storage* s, const std::vector<Uuid>& actors,
@@ -377,6 +378,37 @@ bool parse_gset_ops(const uint8_t* p, size_t n, std::vector<uint64_t>* out);
 // GSet { value: BTreeSet<u64> }: the reader (any order, duplicates) and the canonical writer
 bool read_gset_state(Rd& r, std::vector<uint64_t>* out);
 void write_gset_state(Wr* w, const std::vector<uint64_t>& sorted_members);
+
+// The op-file writers' shared host steps (ce_opfile_host.cpp), in a writer's order: carve, stage,
+// its own size passes and opfile_scan, its encoder, opfile_seal, opfile_store, its fold,
+// opfile_finish.  `who` ("gset apply", "orswot add", "orswot rm") heads the error strings.
+// offs and the four u32 columns clen | xlen | coff | xoff, `stride` (> n_files) words apart from
+// cols, the sealed offsets' column and the data version into L
+void opfile_carve(const ce_core* c, unsigned long long* offs, uint32_t* cols, uint64_t stride, uint64_t* d_file_offs,
+                  OpFileLayout* L);
+// ctx->blob (U bytes of clear text: L->clear), ctx->nonces and ctx->outer_ver reserved; the nonces
+// (null: random ones into *drawn, which must live to the next wait) and kCoreVersion uploaded
+int opfile_stage(ce_core* c, const char* who, uint64_t U, const uint8_t* nonces, std::vector<uint8_t>* drawn,
+                 OpFileLayout* L);
+// clen -> coff and xlen -> xoff over n_files + 1 words; tmp is the writer's own scan scratch
+hipError_t opfile_scan(const OpFileLayout& L, void* tmp, size_t tmp_bytes, hipStream_t s);
+// device_seal of the clear texts into d_files, then one wait for *total = file_offs[n_files] and,
+// with d_word, one more device word
+int opfile_seal(ce_core* c, const char* who, const OpFileLayout& L, uint64_t U, uint8_t* d_files, uint64_t* total,
+                const unsigned long long* d_word = nullptr, uint64_t* word = nullptr);
+// the local actor's slot, *v0 = next_op_versions.get(actor), and with storage the files' download
+// and store as versions v0, v0 + 1, ...
+int opfile_store(ce_core* c, const char* who, const OpFileLayout& L, const uint8_t* d_files, uint64_t total, uint64_t* v0);
+// next_op_versions[local actor] = v0 + F (the slot read again: a growth may have moved it), table_upload
+int opfile_finish(ce_core* c, uint64_t v0, uint32_t F);
+// nothing to write: the one zero offset (d_file_offs null: none), no file, no version
+int opfile_empty(ce_core* c, const char* who, uint64_t* d_file_offs, uint32_t* n_files, uint64_t* bytes);
+// the host forms' way back: total bytes of files and F + 1 offsets from the two device buffers
+int opfile_download(ce_ctx* ctx, const char* who, const DevBuf& files, const DevBuf& offs, uint64_t total, uint32_t F,
+                    std::vector<uint8_t>* out, std::vector<uint64_t>* fo);
+// a malloc'd copy for the caller to ce_buf_free; the files and offsets of a host form (either may be null)
+void fill_buf(ce_buf* out, const void* p, size_t n);
+void fill_files(ce_buf* files, ce_buf* file_offs, const std::vector<uint8_t>& out, const std::vector<uint64_t>& fo);
 
 // LWWReg<u64, u64> (ce_lww_host.cpp): the register lives on the host; next_op_versions, the actor
 // table and the storage plumbing are ce_core.cpp's, as for every kind

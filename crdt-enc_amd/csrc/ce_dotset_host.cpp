@@ -2596,7 +2596,7 @@ bool ow_shape(uint64_t n, uint32_t per_op, uint32_t opf, OwShape* o) {
   // every file but the last holds opf full ops; the last op may be shorter, the last file hold fewer
   const uint64_t rem = n % per_op, last_ops = o->n_ops - (F - 1) * opf;
   const uint64_t full_clear = ow_file_bound(opf, per_op);
-  const uint64_t last_clear = 16 + ow_arr_hdr((uint32_t)last_ops) + (last_ops - 1) * op_full + (rem ? ow_op_bound(rem) : op_full);
+  const uint64_t last_clear = 16 + arr_hdr_len((uint32_t)last_ops) + (last_ops - 1) * op_full + (rem ? ow_op_bound(rem) : op_full);
   o->clear = (F - 1) * full_clear + last_clear;
   o->bytes = (F - 1) * (16 + sealed_len(full_clear)) + 16 + sealed_len(last_clear);
   return true;
@@ -2633,25 +2633,13 @@ int ds_add_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, con
       return ctx->hip_fail(e, "orswot add clock");
   }
   if (sh.n_ops > ~0ull - c0) return ctx->fail(CE_ERR_INVALID_ARG, "orswot add: the local actor's counter would pass 2^64 - 1");
-  if (F == 0) {  // nothing to write: the one offset, no file, no version
-    if ((e = hipMemsetAsync(d_file_offs, 0, 8, s)) || (e = stream_wait(s))) return ctx->hip_fail(e, "orswot add");
-    *n_files = 0;
-    *bytes = 0;
-    return CE_OK;
-  }
+  if (F == 0) return opfile_empty(c, "orswot add", d_file_offs, n_files, bytes);
   const uint64_t U = sh.clear;
   size_t cb = 0;
-  if ((e = ctx->blob.reserve(U + 64)) || (e = d->ow_wr.reserve(8ull * (F + 1) + 8ull * (n_ops + 1) + 16ull * (F + 1) + 64)) ||
-      (e = ctx->nonces.reserve(24ull * F)) || (e = ctx->outer_ver.reserve(64)) ||
+  if ((e = d->ow_wr.reserve(8ull * (F + 1) + 8ull * (n_ops + 1) + 16ull * (F + 1) + 64)) ||
       (e = ds_excl_sum_u32(nullptr, cb, nullptr, nullptr, std::max(n_ops, F) + 1, s)) || (e = d->cub_tmp.reserve(cb + 256)))
     return ctx->hip_fail(e, "orswot add reserve");
   cb = d->cub_tmp.cap;
-  std::vector<uint8_t> nb;
-  if (!nonces) {
-    nb.resize(24ull * F);
-    os_random(nb.data(), nb.size());
-    nonces = nb.data();
-  }
   OwArgs a{};
   a.members = reinterpret_cast<const unsigned long long*>(d_members);
   a.n = n;
@@ -2659,18 +2647,13 @@ int ds_add_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, con
   a.per_op = sh.per_op;
   a.opf = sh.opf;
   a.n_ops = n_ops;
-  a.n_files = F;
-  a.offs = d->ow_wr.as<unsigned long long>();
-  a.olen = reinterpret_cast<uint32_t*>(a.offs + F + 1);
+  a.L.n_files = F;
+  // words: offs (u64 x (F + 1)) | olen | ooff (n_ops + 1 each) | the four file columns of F + 1
+  unsigned long long* offs = d->ow_wr.as<unsigned long long>();
+  a.olen = reinterpret_cast<uint32_t*>(offs + F + 1);
   uint32_t* ooff = a.olen + (n_ops + 1);
-  a.clen = ooff + (n_ops + 1);
-  a.xlen = a.clen + (F + 1);
-  uint32_t* coff = a.xlen + (F + 1);
-  uint32_t* xoff = coff + (F + 1);
   a.ooff = ooff;
-  a.coff = coff;
-  a.xoff = xoff;
-  std::memcpy(a.dv, c->current_data_version.data(), 16);
+  opfile_carve(c, offs, ooff + (n_ops + 1), F + 1, d_file_offs, &a.L);
   {  // an op up to its counter, then a7 "members" (to_vec_named: structs as maps, the variant by name)
     Wr w;
     w.map(1);
@@ -2685,41 +2668,21 @@ int ds_add_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, con
     if (w.b.size() != kOwFixedBytes) return ctx->fail(CE_ERR_DEVICE, "orswot add: op head");
     std::memcpy(a.head, w.b.data(), kOwFixedBytes);
   }
-  a.clear = ctx->blob.as<uint8_t>();
-  a.file_offs = reinterpret_cast<unsigned long long*>(d_file_offs);
-  if ((e = hipMemcpyAsync(ctx->nonces.p, nonces, 24ull * F, hipMemcpyHostToDevice, s)) ||
-      (e = hipMemcpyAsync(ctx->outer_ver.p, kCoreVersion, 16, hipMemcpyHostToDevice, s)))
-    return ctx->hip_fail(e, "orswot add upload");
+  std::vector<uint8_t> drawn;
+  if ((rc = opfile_stage(c, "orswot add", U, nonces, &drawn, &a.L))) return rc;
   int t = ctx->tbegin("orswot_add_sizes");  // (the two size passes and their three scans)
   if ((e = launch_ow_op_sizes(s, a)) || (e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.olen, ooff, n_ops + 1, s)) ||
-      (e = launch_ow_file_sizes(s, a)) || (e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.clen, coff, F + 1, s)) ||
-      (e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.xlen, xoff, F + 1, s)))
+      (e = launch_opfile_sizes(s, a.L, ooff, a.opf, n_ops)) || (e = opfile_scan(a.L, d->cub_tmp.p, d->cub_tmp.cap, s)))
     return ctx->hip_fail(e, "orswot add sizes");
   ctx->tend(t);
   t = ctx->tbegin("orswot_add_encode");
   if ((e = launch_ow_encode(s, a, test_grid_cap()))) return ctx->hip_fail(e, "orswot add encode");
   ctx->tend(t);
-  // file i = CURRENT_VERSION || Cryptor::encrypt(clear_i) (lib.rs:682-695), straight into d_files
-  if ((rc = device_seal(ctx, a.clear, reinterpret_cast<const uint64_t*>(a.offs), F, U, ctx->outer_ver.as<uint8_t>(),
-                        ctx->nonces.as<uint8_t>(), d_files, d_file_offs, key_of(c))))
+  // everything is sealed behind the wait: stored, folded and bumped from there on
+  uint64_t total = 0, v0 = 0;
+  if ((rc = opfile_seal(c, "orswot add", a.L, U, d_files, &total)) ||
+      (rc = opfile_store(c, "orswot add", a.L, d_files, total, &v0)))
     return rc;
-  uint64_t total = 0;
-  if ((e = hipMemcpyAsync(&total, d_file_offs + F, 8, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
-    return ctx->hip_fail(e, "orswot add");
-  // everything is sealed: stored, folded and bumped from here on
-  uint32_t slot;
-  if ((rc = insert_actor(c, c->local_actor, &slot))) return rc;
-  const uint64_t v0 = c->nov[slot];  // next_op_versions.get(actor) (lib.rs:703)
-  if (c->storage) {
-    std::vector<uint8_t> out(total);
-    std::vector<uint64_t> fo(F + 1);
-    if ((e = hipMemcpyAsync(out.data(), d_files, total, hipMemcpyDeviceToHost, s)) ||
-        (e = hipMemcpyAsync(fo.data(), d_file_offs, 8ull * (F + 1), hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
-      return ctx->hip_fail(e, "orswot add download");
-    for (uint32_t i = 0; i < F; i++)
-      if ((rc = storage_store_op(c->storage, c->local_actor, v0 + i, out.data() + fo[i], fo[i + 1] - fo[i])))
-        return ctx->fail(rc, "failed writing ops file");
-  }
   // state.apply(op) for op in ops (lib.rs:710-712): the fold's add columns filled from the column
   // in HBM.  Short ops go in as they are, one add an op.  Long ops go in as one add a member, the
   // members of an op sharing its dot: the same entries and clock, but the fold's kernels take a
@@ -2744,7 +2707,7 @@ int ds_add_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, con
   oc.per_op = sh.per_op;
   oc.span = span;
   oc.n_add = n_add;
-  oc.actor_id = actor_id_of_slot(c, slot);
+  oc.actor_id = actor_id_of_slot(c, c->slot_of.at(c->local_actor));
   oc.add_actor = o.add_actor;
   oc.add_ctr = o.add_ctr;
   oc.add_mbeg = o.add_mbeg;
@@ -2768,14 +2731,12 @@ int ds_add_members_device(ce_core* c, const uint64_t* d_members, uint64_t n, con
     d->poisoned = true;
     return rc;
   }
-  slot = c->slot_of.at(c->local_actor);
-  c->nov[slot] = v0 + F;  // next_op_versions.inc(actor), once a file (lib.rs:714-715)
   c->path_counts["orswot_add_device_files"] += F;
   c->path_counts["orswot_add_device_ops"] += n_ops;
   c->path_counts["orswot_add_device_members"] += n;
   *n_files = F;
   *bytes = total;
-  return table_upload(c);
+  return opfile_finish(c, v0, F);
 }
 
 int ds_add_members_host(ce_core* c, const uint64_t* members, uint64_t n, const OwShape& sh, const uint8_t* nonces,
@@ -2793,13 +2754,8 @@ int ds_add_members_host(ce_core* c, const uint64_t* members, uint64_t n, const O
   if (int rc = ds_add_members_device(c, d->ow_col.as<uint64_t>(), n, sh, nonces, d->ow_files.as<uint8_t>(),
                                      d->ow_offs.as<uint64_t>(), &F, &total))
     return rc;
-  out->resize(total);
-  fo->resize(F + 1);
-  if ((total && (e = hipMemcpyAsync(out->data(), d->ow_files.p, total, hipMemcpyDeviceToHost, s))) ||
-      (e = hipMemcpyAsync(fo->data(), d->ow_offs.p, 8ull * (F + 1), hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
-    return ctx->hip_fail(e, "orswot add download");
   *n_files = F;
-  return CE_OK;
+  return opfile_download(ctx, "orswot add", d->ow_files, d->ow_offs, total, F, out, fo);
 }
 
 // actor UUIDs and UUID-order ranks by stable id, in HBM and on the host (kept: next_op_versions
@@ -2861,12 +2817,9 @@ int ds_rm_members_device(ce_core* c, const uint64_t* d_members, uint64_t n64, ui
   if (opf == 0) opf = 16;
   if ((rc = ds_settle(c))) return rc;
   const uint32_t n = (uint32_t)n64;
-  auto nothing = [&]() -> int {  // no op to write: the one offset, no file, no version
-    if (!sizing && ((e = hipMemsetAsync(d_file_offs, 0, 8, s)) || (e = stream_wait(s)))) return ctx->hip_fail(e, "orswot rm");
+  auto nothing = [&]() -> int {  // no op to write (the sizing call has no offset column)
     *n_ops_out = 0;
-    *n_files = 0;
-    *bytes = 0;
-    return CE_OK;
+    return opfile_empty(c, "orswot rm", sizing ? nullptr : d_file_offs, n_files, bytes);
   };
   if (n == 0) return nothing();
   const uint64_t slots = (uint64_t)d->mcap_s + d->pcap + 1;
@@ -2894,8 +2847,8 @@ int ds_rm_members_device(ce_core* c, const uint64_t* d_members, uint64_t n64, ui
   a.live_only = flags & CE_ORSWOT_RM_LIVE_ONLY ? 1u : 0u;
   a.first = d->rm_first.as<uint32_t>();
   a.tot = d->rm_wr.as<unsigned long long>();
-  a.offs = a.tot + kRmTotN;
-  uint32_t* w = reinterpret_cast<uint32_t*>(a.offs + n1);
+  unsigned long long* offs = a.tot + kRmTotN;
+  uint32_t* w = reinterpret_cast<uint32_t*>(offs + n1);
   a.hnd = w;
   a.cnt = w + n1;
   a.ebytes = w + 2 * n1;
@@ -2906,15 +2859,10 @@ int ds_rm_members_device(ce_core* c, const uint64_t* d_members, uint64_t n64, ui
   a.op_pos = w + 7 * n1;
   a.olen = w + 8 * n1;
   uint32_t* ooff = w + 9 * n1;
-  a.clen = w + 10 * n1;
-  a.xlen = w + 11 * n1;
-  uint32_t* coff = w + 12 * n1;
-  uint32_t* xoff = w + 13 * n1;
+  opfile_carve(c, offs, w + 10 * n1, n1, d_file_offs, &a.L);
   a.kpos = kpos;
   a.ebeg = ebeg;
   a.ooff = ooff;
-  a.coff = coff;
-  a.xoff = xoff;
   a.rank_of_id = d->rank_of_id.as<uint32_t>();
   a.id_of_rank = d->id_of_rank.as<uint32_t>();
   a.uuid_of_id = d->uuid_of_id.as<uint8_t>();
@@ -2951,21 +2899,20 @@ int ds_rm_members_device(ce_core* c, const uint64_t* d_members, uint64_t n64, ui
     return nothing();
   }
   a.n_ops = n_ops;
-  a.n_files = F;
+  a.L.n_files = F;
   a.n_ent = (uint32_t)E;
   // 2) sizes: op lengths, file lengths and their sealed extras, from the first scan alone
   t = ctx->tbegin("orswot_rm_sizes");
   if ((e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.keep, kpos, n + 1, s)) || (e = launch_rm_scatter(s, a)) ||
       (e = launch_rm_op_sizes(s, a)) || (e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.olen, ooff, n_ops + 1, s)) ||
-      (e = launch_rm_file_sizes(s, a)) || (e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.clen, coff, F + 1, s)) ||
-      (e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.xlen, xoff, F + 1, s)))
+      (e = launch_opfile_sizes(s, a.L, ooff, opf, n_ops)) || (e = opfile_scan(a.L, d->cub_tmp.p, d->cub_tmp.cap, s)))
     return ctx->hip_fail(e, "orswot rm sizes");
   ctx->tend(t);
   uint32_t ends[2] = {0, 0};
-  if ((e = hipMemcpyAsync(&ends[0], coff + F, 4, hipMemcpyDeviceToHost, s)) ||
-      (e = hipMemcpyAsync(&ends[1], xoff + F, 4, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
+  if ((e = hipMemcpyAsync(&ends[0], a.L.coff + F, 4, hipMemcpyDeviceToHost, s)) ||
+      (e = hipMemcpyAsync(&ends[1], a.L.xoff + F, 4, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
     return ctx->hip_fail(e, "orswot rm sizes");
-  const uint64_t U = ends[0], total = U + (uint64_t)F * kOwSealBase + ends[1];
+  const uint64_t U = ends[0], total = U + (uint64_t)F * kOpFileSealBase + ends[1];
   if (sizing) {
     *n_ops_out = n_ops;
     *n_files = F;
@@ -2978,8 +2925,7 @@ int ds_rm_members_device(ce_core* c, const uint64_t* d_members, uint64_t n64, ui
   const int key_bits = bits_for(n) + a.rank_bits;
   if ((e = d->rm_ent.reserve(44ull * E + 256)) ||
       (E && (e = sort_pairs_u64(nullptr, sb, nullptr, nullptr, nullptr, nullptr, a.n_ent, key_bits, s))) ||
-      (e = d->cub_tmp.reserve(std::max(sb, cb) + 256)) || (e = ctx->blob.reserve(U + 64)) ||
-      (e = ctx->nonces.reserve(24ull * F)) || (e = ctx->outer_ver.reserve(64)))
+      (e = d->cub_tmp.reserve(std::max(sb, cb) + 256)))
     return ctx->hip_fail(e, "orswot rm reserve");
   cb = sb = d->cub_tmp.cap;
   a.key = d->rm_ent.as<unsigned long long>();
@@ -2991,13 +2937,6 @@ int ds_rm_members_device(ce_core* c, const uint64_t* d_members, uint64_t n64, ui
   a.s_actor = sidx + E;
   a.skey = skey;
   a.sidx = sidx;
-  std::vector<uint8_t> nb;
-  if (!nonces) {
-    nb.resize(24ull * F);
-    os_random(nb.data(), nb.size());
-    nonces = nb.data();
-  }
-  std::memcpy(a.dv, c->current_data_version.data(), 16);
   {  // an op up to its clock's map header, then a7 "members" 91 (to_vec_named: structs as maps, the variant by name)
     Wr hw;
     hw.map(1);
@@ -3012,11 +2951,8 @@ int ds_rm_members_device(ce_core* c, const uint64_t* d_members, uint64_t n64, ui
     if (hw.b.size() != kRmFixedBytes) return leave(CE_ERR_DEVICE, "orswot rm: op head");
     std::memcpy(a.head, hw.b.data(), kRmFixedBytes);
   }
-  a.clear = ctx->blob.as<uint8_t>();
-  a.file_offs = reinterpret_cast<unsigned long long*>(d_file_offs);
-  if ((e = hipMemcpyAsync(ctx->nonces.p, nonces, 24ull * F, hipMemcpyHostToDevice, s)) ||
-      (e = hipMemcpyAsync(ctx->outer_ver.p, kCoreVersion, 16, hipMemcpyHostToDevice, s)))
-    return ctx->hip_fail(e, "orswot rm upload");
+  std::vector<uint8_t> drawn;
+  if ((rc = opfile_stage(c, "orswot rm", U, nonces, &drawn, &a.L))) return rc;
   t = ctx->tbegin("orswot_rm_clocks");
   if ((e = ds_excl_sum_u32(d->cub_tmp.p, cb, a.cnt, ebeg, n + 1, s)) || (e = launch_rm_gather(s, a)) ||
       (e = launch_rm_unmark(s, a)) ||
@@ -3029,29 +2965,11 @@ int ds_rm_members_device(ce_core* c, const uint64_t* d_members, uint64_t n64, ui
   t = ctx->tbegin("orswot_rm_encode");
   if ((e = launch_rm_encode(s, a, test_grid_cap()))) return ctx->hip_fail(e, "orswot rm encode");
   ctx->tend(t);
-  // file i = CURRENT_VERSION || Cryptor::encrypt(clear_i) (lib.rs:682-695), straight into d_files
-  if ((rc = device_seal(ctx, a.clear, reinterpret_cast<const uint64_t*>(a.offs), F, U, ctx->outer_ver.as<uint8_t>(),
-                        ctx->nonces.as<uint8_t>(), d_files, d_file_offs, key_of(c))))
-    return rc;
-  uint64_t sealed = 0, gathered = 0;
-  if ((e = hipMemcpyAsync(&sealed, d_file_offs + F, 8, hipMemcpyDeviceToHost, s)) ||
-      (e = hipMemcpyAsync(&gathered, a.tot + kRmTotGather, 8, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
-    return ctx->hip_fail(e, "orswot rm");
+  uint64_t sealed = 0, gathered = 0, v0 = 0;
+  if ((rc = opfile_seal(c, "orswot rm", a.L, U, d_files, &sealed, a.tot + kRmTotGather, &gathered))) return rc;
   if (sealed != total || gathered != E) return ctx->fail(CE_ERR_DEVICE, "orswot rm: the two scans disagree");
   // everything is sealed: stored, folded and bumped from here on
-  uint32_t slot;
-  if ((rc = insert_actor(c, c->local_actor, &slot))) return rc;
-  const uint64_t v0 = c->nov[slot];  // next_op_versions.get(actor) (lib.rs:703)
-  if (c->storage) {
-    std::vector<uint8_t> out(total);
-    std::vector<uint64_t> fo(F + 1);
-    if ((e = hipMemcpyAsync(out.data(), d_files, total, hipMemcpyDeviceToHost, s)) ||
-        (e = hipMemcpyAsync(fo.data(), d_file_offs, 8ull * (F + 1), hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
-      return ctx->hip_fail(e, "orswot rm download");
-    for (uint32_t i = 0; i < F; i++)
-      if ((rc = storage_store_op(c->storage, c->local_actor, v0 + i, out.data() + fo[i], fo[i + 1] - fo[i])))
-        return ctx->fail(rc, "failed writing ops file");
-  }
+  if ((rc = opfile_store(c, "orswot rm", a.L, d_files, total, &v0))) return rc;
   // state.apply(op) for op in ops (lib.rs:710-712): the fold's removal columns filled from the
   // sorted entries in HBM, one removal a position of the column.  Only a member's first position
   // carries its clock: a second identical Rm is idempotent (it removes dots the first has
@@ -3089,15 +3007,13 @@ int ds_rm_members_device(ce_core* c, const uint64_t* d_members, uint64_t n64, ui
     d->poisoned = true;
     return rc;
   }
-  slot = c->slot_of.at(c->local_actor);
-  c->nov[slot] = v0 + F;  // next_op_versions.inc(actor), once a file (lib.rs:714-715)
   c->path_counts["orswot_rm_device_files"] += F;
   c->path_counts["orswot_rm_device_ops"] += n_ops;
   c->path_counts["orswot_rm_device_entries"] += tot[kRmTotOpEntries];
   *n_ops_out = n_ops;
   *n_files = F;
   *bytes = total;
-  return table_upload(c);
+  return opfile_finish(c, v0, F);
 }
 
 int ds_rm_members_host(ce_core* c, const uint64_t* members, uint64_t n, uint32_t opf, uint32_t flags, const uint8_t* nonces,
@@ -3120,13 +3036,8 @@ int ds_rm_members_host(ce_core* c, const uint64_t* members, uint64_t n, uint32_t
   if ((rc = ds_rm_members_device(c, d->ow_col.as<uint64_t>(), n, opf, flags, nonces, d->ow_files.as<uint8_t>(), total + 64,
                                  d->ow_offs.as<uint64_t>(), &n_ops, &F, &total)))
     return rc;
-  out->resize(total);
-  fo->resize(F + 1);
-  if ((total && (e = hipMemcpyAsync(out->data(), d->ow_files.p, total, hipMemcpyDeviceToHost, s))) ||
-      (e = hipMemcpyAsync(fo->data(), d->ow_offs.p, 8ull * (F + 1), hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
-    return ctx->hip_fail(e, "orswot rm download");
   *n_files = F;
-  return CE_OK;
+  return opfile_download(ctx, "orswot rm", d->ow_files, d->ow_offs, total, F, out, fo);
 }
 
 // Compaction of an Orswot state without bringing the entries to the host: the clear text

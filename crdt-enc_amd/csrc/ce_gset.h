@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "ce_kernels.h"
+#include "ce_opfile.h"
 
 namespace ce {
 
@@ -108,19 +109,8 @@ struct GsFilesArgs {
   const unsigned long long* members;  // [n]
   unsigned long long n;
   uint32_t per_file;
-  uint32_t n_files;            // ceil(n / per_file) > 0
-  uint32_t* clen;              // [n_files + 1] clear lengths, clen[n_files] = 0 (the size pass)
-  uint32_t* xlen;              // [n_files + 1] a sealed file's bytes past its clear text and kGsSealBase
-  const uint32_t* coff;        // [n_files + 1] exclusive sums of clen (the encoder)
-  const uint32_t* xoff;        //               and of xlen
-  uint8_t dv[16];              // the data version
-  uint8_t* clear;              // the clear texts back to back, 16-byte aligned
-  unsigned long long* offs;    // [n_files + 1] clear offsets for the seal
-  unsigned long long* file_offs;  // [n_files + 1] sealed offsets: coff + i * kGsSealBase + xoff
+  OpFileLayout L;              // n_files = ceil(n / per_file) > 0 (ce_opfile.h)
 };
-// the least a sealed file adds to its clear text: the outer version and an envelope whose two bin
-// headers are bin8
-static constexpr uint64_t kGsSealBase = 16 + sealed_len(0);
 hipError_t launch_gs_file_sizes(hipStream_t s, const GsFilesArgs& a);
 // grid_cap: the most blocks to launch (0: the default)
 hipError_t launch_gs_files_encode(hipStream_t s, const GsFilesArgs& a, uint32_t grid_cap);

@@ -355,9 +355,9 @@ __global__ __launch_bounds__(256) void k_gs_contains(GsTable t, const unsigned l
   }
 }
 
-// the serializer: an element's encoded length (gs_width: its smallest unsigned form), and the writer
+// the serializer: an element's encoded length (uint_width: its smallest unsigned form), and the writer
 __global__ __launch_bounds__(256) void k_gs_widths(const unsigned long long* v, uint32_t n, uint32_t* w) {
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) w[i] = gs_width(v[i]);
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) w[i] = uint_width(v[i]);
 }
 
 // element i at out[off[i]]; the last element's thread writes the clear length (head_len + the
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256) void k_gs_write(const unsigned long long* v, c
                                                   unsigned long long head_len) {
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     const unsigned long long x = v[i];
-    const uint32_t w = gs_width(x);
+    const uint32_t w = uint_width(x);
     uint8_t* p = out + off[i];
     if (w == 1) p[0] = (uint8_t)x;
     else {

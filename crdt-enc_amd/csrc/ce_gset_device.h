@@ -61,9 +61,4 @@ __device__ __forceinline__ void gs_put(const GsTable& committed, const GsTable& 
   gs_insert(batch, v);
 }
 
-// an element's encoded length: its smallest unsigned form (fixint, cc, cd, ce, cf)
-__device__ __forceinline__ uint32_t gs_width(unsigned long long v) {
-  return v <= 0x7f ? 1u : v <= 0xff ? 2u : v <= 0xffff ? 3u : v <= 0xffffffffull ? 5u : 9u;
-}
-
 }  // namespace ce

@@ -684,8 +684,6 @@ int gs_compact_device(ce_core* c, std::vector<uint8_t> head, const uint8_t* oute
 
 namespace {
 
-constexpr uint64_t arr_hdr_len(uint64_t cnt) { return cnt <= 15 ? 1 : 3; }  // (cnt <= kGsFileMembers)
-
 // a column of n members at per_file (0: kGsFileMembers) members a file: the files, the most bytes
 // they take sealed (every member 9 bytes wide), and the clear texts' bound 19 F + 9 n; false:
 // per_file out of range, or more files than a u32 counts
@@ -695,8 +693,8 @@ bool apply_bound(uint64_t n, uint32_t* per_file, uint32_t* files, uint64_t* byte
   const uint64_t pf = *per_file, full = n / pf, rem = n % pf, F = full + (rem ? 1 : 0);
   if (F > 0xffffffffull) return false;
   *files = (uint32_t)F;
-  *bytes = full * (16 + sealed_len(16 + arr_hdr_len(pf) + 9 * pf)) +
-           (rem ? 16 + sealed_len(16 + arr_hdr_len(rem) + 9 * rem) : 0);
+  *bytes = full * (16 + sealed_len(16 + arr_hdr_len((uint32_t)pf) + 9 * pf)) +
+           (rem ? 16 + sealed_len(16 + arr_hdr_len((uint32_t)rem) + 9 * rem) : 0);
   *clear_bound = 19 * F + 9 * n;
   return true;
 }
@@ -769,87 +767,46 @@ int gs_apply_members_device(ce_core* c, const uint64_t* d_members, uint64_t n_in
     n = m;
   }
   const uint32_t F = (n + per_file - 1) / per_file;
-  if (F == 0) {  // nothing to write: the one offset, no file, no version
-    if ((e = hipMemsetAsync(d_file_offs, 0, 8, s)) || (e = stream_wait(s))) return ctx->hip_fail(e, "gset apply");
-    *n_files = 0;
-    *bytes = 0;
-    return CE_OK;
-  }
+  if (F == 0) return opfile_empty(c, "gset apply", d_file_offs, n_files, bytes);
   // room for every member before anything is sealed: the insert below cannot meet the load bound
   uint32_t hm[kMetaWords];
   if ((rc = read_meta(c, hm)) || (rc = ensure_committed(c, hm[kGsCount], n))) return rc;
   const uint64_t U = 19ull * F + 9ull * n;
   size_t cb = 0;
-  if ((e = ctx->blob.reserve(U + 64)) || (e = g->wr.reserve(24ull * (F + 1) + 64)) ||
-      (e = ctx->nonces.reserve(24ull * F)) || (e = ctx->outer_ver.reserve(64)) ||
-      (e = ds_excl_sum_u32(nullptr, cb, nullptr, nullptr, F + 1, s)) || (e = g->scan_tmp.reserve(cb + 256)))
+  if ((e = g->wr.reserve(24ull * (F + 1) + 64)) || (e = ds_excl_sum_u32(nullptr, cb, nullptr, nullptr, F + 1, s)) ||
+      (e = g->scan_tmp.reserve(cb + 256)))
     return ctx->hip_fail(e, "gset apply reserve");
-  cb = g->scan_tmp.cap;
-  std::vector<uint8_t> nb;
-  if (!nonces) {
-    nb.resize(24ull * F);
-    os_random(nb.data(), nb.size());
-    nonces = nb.data();
-  }
   GsFilesArgs a{};
   a.members = col;
   a.n = n;
   a.per_file = per_file;
-  a.n_files = F;
-  a.offs = g->wr.as<unsigned long long>();
-  a.clen = reinterpret_cast<uint32_t*>(a.offs + F + 1);
-  a.xlen = a.clen + (F + 1);
-  uint32_t* coff = a.xlen + (F + 1);
-  uint32_t* xoff = coff + (F + 1);
-  a.coff = coff;
-  a.xoff = xoff;
-  std::memcpy(a.dv, c->current_data_version.data(), 16);
-  a.clear = ctx->blob.as<uint8_t>();
-  a.file_offs = reinterpret_cast<unsigned long long*>(d_file_offs);
-  if ((e = hipMemcpyAsync(ctx->nonces.p, nonces, 24ull * F, hipMemcpyHostToDevice, s)) ||
-      (e = hipMemcpyAsync(ctx->outer_ver.p, kCoreVersion, 16, hipMemcpyHostToDevice, s)))
-    return ctx->hip_fail(e, "gset apply upload");
+  a.L.n_files = F;
+  unsigned long long* offs = g->wr.as<unsigned long long>();
+  opfile_carve(c, offs, reinterpret_cast<uint32_t*>(offs + F + 1), F + 1, d_file_offs, &a.L);
+  std::vector<uint8_t> drawn;
+  if ((rc = opfile_stage(c, "gset apply", U, nonces, &drawn, &a.L))) return rc;
   int t = ctx->tbegin("gset_apply_sizes");  // (the size pass and its two scans)
-  if ((e = launch_gs_file_sizes(s, a)) || (e = ds_excl_sum_u32(g->scan_tmp.p, cb, a.clen, coff, F + 1, s)) ||
-      (e = ds_excl_sum_u32(g->scan_tmp.p, cb, a.xlen, xoff, F + 1, s)))
+  if ((e = launch_gs_file_sizes(s, a)) || (e = opfile_scan(a.L, g->scan_tmp.p, g->scan_tmp.cap, s)))
     return ctx->hip_fail(e, "gset apply sizes");
   ctx->tend(t);
   t = ctx->tbegin("gset_apply_encode");
   if ((e = launch_gs_files_encode(s, a, test_grid_cap()))) return ctx->hip_fail(e, "gset apply encode");
   ctx->tend(t);
-  // file i = CURRENT_VERSION || Cryptor::encrypt(clear_i) (lib.rs:682-695), straight into d_files
-  if ((rc = device_seal(ctx, a.clear, reinterpret_cast<const uint64_t*>(a.offs), F, U, ctx->outer_ver.as<uint8_t>(),
-                        ctx->nonces.as<uint8_t>(), d_files, d_file_offs, key_of(c))))
+  // everything is sealed behind the wait: stored, inserted and bumped from there on
+  uint64_t total = 0, v0 = 0;
+  if ((rc = opfile_seal(c, "gset apply", a.L, U, d_files, &total)) ||
+      (rc = opfile_store(c, "gset apply", a.L, d_files, total, &v0)))
     return rc;
-  uint64_t total = 0;
-  if ((e = hipMemcpyAsync(&total, d_file_offs + F, 8, hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
-    return ctx->hip_fail(e, "gset apply");
-  // everything is sealed: stored, inserted and bumped from here on
-  uint32_t slot;
-  if ((rc = insert_actor(c, c->local_actor, &slot))) return rc;
-  const uint64_t v0 = c->nov[slot];  // next_op_versions.get(actor) (lib.rs:703)
-  if (c->storage) {
-    std::vector<uint8_t> out(total);
-    std::vector<uint64_t> fo(F + 1);
-    if ((e = hipMemcpyAsync(out.data(), d_files, total, hipMemcpyDeviceToHost, s)) ||
-        (e = hipMemcpyAsync(fo.data(), d_file_offs, 8ull * (F + 1), hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
-      return ctx->hip_fail(e, "gset apply download");
-    for (uint32_t i = 0; i < F; i++)
-      if ((rc = storage_store_op(c->storage, c->local_actor, v0 + i, out.data() + fo[i], fo[i + 1] - fo[i])))
-        return ctx->fail(rc, "failed writing ops file");
-  }
   // state.apply(op) for op in ops (lib.rs:710-712): from the column, or the survivors, in HBM
   t = ctx->tbegin("gset_apply_insert");
   if ((e = launch_gs_insert(s, committed(g), col, n))) return ctx->hip_fail(e, "gset apply insert");
   ctx->tend(t);
   if ((e = stream_wait(s))) return ctx->hip_fail(e, "gset apply insert");  // (the column is the caller's)
-  slot = c->slot_of.at(c->local_actor);
-  c->nov[slot] = v0 + F;  // next_op_versions.inc(actor), once a file (lib.rs:714-715)
   c->path_counts["gset_apply_device_files"] += F;
   c->path_counts["gset_apply_device_members"] += n;
   *n_files = F;
   *bytes = total;
-  return table_upload(c);
+  return opfile_finish(c, v0, F);
 }
 
 namespace {
@@ -1155,21 +1112,10 @@ int ce_core_gset_apply_members(ce_core* c, const uint64_t* members, uint64_t n, 
   if ((rc = gs_apply_members_device(c, g->up_col.as<uint64_t>(), n, per_file, flags, nonces, g->up_files.as<uint8_t>(),
                                     g->up_offs.as<uint64_t>(), &F, &total)))
     return rc;
-  std::vector<uint8_t> out(total);
-  std::vector<uint64_t> fo(F + 1);
-  if ((total && (e = hipMemcpyAsync(out.data(), g->up_files.p, total, hipMemcpyDeviceToHost, s))) ||
-      (e = hipMemcpyAsync(fo.data(), g->up_offs.p, 8ull * (F + 1), hipMemcpyDeviceToHost, s)) || (e = stream_wait(s)))
-    return ctx->hip_fail(e, "gset apply download");
-  if (files) {
-    files->data = (uint8_t*)malloc(out.size() ? out.size() : 1);
-    std::memcpy(files->data, out.data(), out.size());
-    files->len = out.size();
-  }
-  if (file_offs) {
-    file_offs->data = (uint8_t*)malloc(fo.size() * 8);
-    std::memcpy(file_offs->data, fo.data(), fo.size() * 8);
-    file_offs->len = fo.size() * 8;
-  }
+  std::vector<uint8_t> out;
+  std::vector<uint64_t> fo;
+  if ((rc = opfile_download(ctx, "gset apply", g->up_files, g->up_offs, total, F, &out, &fo))) return rc;
+  fill_files(files, file_offs, out, fo);
   *n_files = F;
   return CE_OK;
 }

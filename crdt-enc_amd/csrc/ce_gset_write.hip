@@ -10,122 +10,68 @@
 
 #include "ce_gset.h"
 #include "ce_gset_device.h"
+#include "ce_opfile_device.h"
 
 namespace ce {
 namespace {
 
-constexpr uint32_t kGroup = 16;       // lanes per file, the readers' geometry
+constexpr uint32_t kGroup = kOpFileGroup;
 constexpr uint32_t kWaveFiles = 4;    // files per wave and trip
 constexpr uint32_t kPage = 4096;      // the longest clear text: 16 + 3 + 9 * kGsFileMembers
 static_assert(16 + 3 + 9 * kGsFileMembers <= kPage, "a file's clear text is one page");
 // the wave's files lie back to back in the clear blob; they are staged at the same offset mod 16
 constexpr uint32_t kStageBytes = kWaveFiles * kPage + 16;
 
-__device__ __forceinline__ uint32_t arr_hdr_len(uint32_t cnt) { return cnt <= 15 ? 1u : 3u; }  // (cnt < 65536)
-
 // members of file f (0 past the last file)
 __device__ __forceinline__ uint32_t file_count(const GsFilesArgs& a, uint32_t f) {
-  if (f >= a.n_files) return 0;
+  if (f >= a.L.n_files) return 0;
   const unsigned long long left = a.n - (unsigned long long)f * a.per_file;
   return left < a.per_file ? (uint32_t)left : a.per_file;
 }
 
-// The size pass: one 16-lane group per file sums its members' widths (lane sub: members
-// sub + 16 j).  Every lane of a block runs the same trips, so the shuffles see whole groups.
+// The size pass: one 16-lane group per file sums its members' widths.  Every lane of a block runs
+// the same trips, so the shuffles see whole groups.
 __global__ __launch_bounds__(256) void k_gs_file_sizes(GsFilesArgs a) {
   const uint32_t sub = threadIdx.x & (kGroup - 1);
   const uint32_t per_block = 256 / kGroup;
-  if (blockIdx.x == 0 && threadIdx.x == 0) a.clen[a.n_files] = a.xlen[a.n_files] = 0;
-  for (uint32_t base = blockIdx.x * per_block; base < a.n_files; base += gridDim.x * per_block) {
+  const uint32_t F = a.L.n_files;
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.L.clen[F] = a.L.xlen[F] = 0;
+  for (uint32_t base = blockIdx.x * per_block; base < F; base += gridDim.x * per_block) {
     const uint32_t f = base + threadIdx.x / kGroup;
     const uint32_t cnt = file_count(a, f);
-    const unsigned long long* m = a.members + (unsigned long long)f * a.per_file;
-    uint32_t sum = 0;
-    for (uint32_t e = sub; e < cnt; e += kGroup) sum += gs_width(m[e]);
-#pragma unroll
-    for (int d = 1; d < (int)kGroup; d <<= 1) sum += (uint32_t)__shfl_xor((int)sum, d, kGroup);
-    if (f < a.n_files && sub == 0) {
-      const uint32_t len = 16 + arr_hdr_len(cnt) + sum;
-      a.clen[f] = len;
-      a.xlen[f] = (uint32_t)(16 + sealed_len(len) - len - kGsSealBase);
-    }
+    const uint32_t sum = group_width_sum(a.members + (unsigned long long)f * a.per_file, cnt, sub);
+    if (f < F && sub == 0) opfile_set_sizes(a.L, f, 16 + arr_hdr_len(cnt) + sum);
   }
 }
 
 // The encoder: one wave per block, kWaveFiles files per trip.  Group q stages file f0 + q in LDS:
-// the data version, the header, then its members 16 to a round, a 16-lane prefix of the widths
-// carrying the running byte offset.  The wave's files are one byte range [c0, c1) of the clear
-// blob, staged at c0's offset mod 16, so the range leaves as aligned 16-byte stores; only its
-// first and last partial chunk, shared with the neighbouring waves' ranges, leave byte by byte.
+// the data version, the header, then its members (group_put_members).  The wave's files are one
+// byte range [c0, c1) of the clear blob, staged at c0's offset mod 16 (opfile_flush).
 __global__ __launch_bounds__(64) void k_gs_files_encode(GsFilesArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
   const uint32_t lane = threadIdx.x, q = lane / kGroup, sub = lane & (kGroup - 1);
-  const uint32_t F = a.n_files;
+  const uint32_t F = a.L.n_files;
   const uint32_t trips = (F + kWaveFiles - 1) / kWaveFiles;
   const uint32_t rounds = (a.per_file + kGroup - 1) / kGroup;
   for (uint32_t w = blockIdx.x; w < trips; w += gridDim.x) {
     const uint32_t f0 = w * kWaveFiles;
     const uint32_t f1 = f0 + kWaveFiles < F ? f0 + kWaveFiles : F;
-    const uint32_t c0 = a.coff[f0], c1 = a.coff[f1];
-    const uint32_t shift = c0 & 15;
+    const uint32_t c0 = a.L.coff[f0], c1 = a.L.coff[f1];  // c1 - c0 <= kWaveFiles * kPage
     const uint32_t f = f0 + q;
-    const bool mine = f < F;
     const uint32_t cnt = file_count(a, f);
     uint32_t at = 0;  // the file's first byte in the stage
-    if (mine) {
-      const uint32_t cf = a.coff[f];
-      at = shift + (cf - c0);
+    if (f < F) {
+      at = (c0 & 15) + (a.L.coff[f] - c0);
       if (sub == 0) {
-        a.offs[f] = cf;
-        a.file_offs[f] = (unsigned long long)cf + (unsigned long long)f * kGsSealBase + a.xoff[f];
-        if (f == F - 1) {
-          a.offs[F] = a.coff[F];
-          a.file_offs[F] = (unsigned long long)a.coff[F] + (unsigned long long)F * kGsSealBase + a.xoff[F];
-        }
-        if (cnt <= 15) stage[at + 16] = (uint8_t)(0x90 | cnt);
-        else {
-          stage[at + 16] = 0xdc;
-          stage[at + 17] = (uint8_t)(cnt >> 8);
-          stage[at + 18] = (uint8_t)cnt;
-        }
+        opfile_publish_offsets(a.L, f);
+        const uint32_t hc = arr_hdr_len(cnt);
+        for (uint32_t k = 0; k < hc; k++) stage[at + 16 + k] = arr_hdr_byte(cnt, hc, k);
       }
-      stage[at + sub] = a.dv[sub];
+      stage[at + sub] = a.L.dv[sub];
     }
-    const unsigned long long* m = a.members + (unsigned long long)f * a.per_file;
-    uint32_t run = at + 16 + arr_hdr_len(cnt);
-    for (uint32_t r = 0; r < rounds; r++) {  // (the same trips in every lane: whole groups shuffle)
-      const uint32_t e = r * kGroup + sub;
-      const bool has = e < cnt;
-      const unsigned long long x = has ? m[e] : 0ull;
-      const uint32_t wd = has ? gs_width(x) : 0u;
-      uint32_t incl = wd;
-#pragma unroll
-      for (int d = 1; d < (int)kGroup; d <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, d, kGroup);
-        if (sub >= (uint32_t)d) incl += t;
-      }
-      const uint32_t total = (uint32_t)__shfl((int)incl, kGroup - 1, kGroup);
-      if (has) {
-        uint8_t* p = stage + run + incl - wd;
-        if (wd == 1) p[0] = (uint8_t)x;
-        else {
-          p[0] = (uint8_t)(wd == 2 ? 0xcc : wd == 3 ? 0xcd : wd == 5 ? 0xce : 0xcf);
-          for (uint32_t k = 1; k < wd; k++) p[k] = (uint8_t)(x >> (8 * (wd - 1 - k)));
-        }
-      }
-      run += total;
-    }
+    group_put_members(stage, at + 16 + arr_hdr_len(cnt), a.members + (unsigned long long)f * a.per_file, cnt, rounds, sub);
     __syncthreads();
-    const uint32_t end = shift + (c1 - c0);  // <= 15 + kWaveFiles * kPage < kStageBytes
-    uint8_t* g16 = a.clear + (c0 - shift);    // 16-byte aligned: stage[b] belongs at g16[b]
-    for (uint32_t lo = lane * 16; lo < end; lo += 64 * 16) {
-      if (lo >= shift && lo + 16 <= end) {
-        *reinterpret_cast<uint4*>(g16 + lo) = *reinterpret_cast<const uint4*>(stage + lo);
-      } else {
-        const uint32_t b0 = lo < shift ? shift : lo, b1 = lo + 16 < end ? lo + 16 : end;
-        for (uint32_t b = b0; b < b1; b++) g16[b] = stage[b];
-      }
-    }
+    opfile_flush(stage, a.L.clear, c0 & ~15u, c0, c1, lane);
     __syncthreads();  // the stage is rewritten by the next trip
   }
 }
@@ -172,37 +118,32 @@ __global__ __launch_bounds__(256) void k_gs_new_compact(const unsigned long long
     if (keep[i]) out[pos[i]] = s[i];
 }
 
-uint32_t blocks_for(uint64_t work, uint32_t per_block, uint32_t cap) {
-  const uint64_t b = (work + per_block - 1) / per_block;
-  return b < 1 ? 1u : (b > cap ? cap : (uint32_t)b);
-}
-
 }  // namespace
 
 hipError_t launch_gs_file_sizes(hipStream_t s, const GsFilesArgs& a) {
-  if (a.n_files == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_gs_file_sizes, dim3(blocks_for(a.n_files, 256 / kGroup, 4096)), dim3(256), 0, s, a);
+  if (a.L.n_files == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_gs_file_sizes, dim3(grid_blocks(a.L.n_files, 256 / kGroup, 4096)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_gs_files_encode(hipStream_t s, const GsFilesArgs& a, uint32_t grid_cap) {
-  if (a.n_files == 0) return hipSuccess;
+  if (a.L.n_files == 0) return hipSuccess;
   // 16 KiB of LDS a block: nine blocks a CU
-  hipLaunchKernelGGL(k_gs_files_encode, dim3(blocks_for(a.n_files, kWaveFiles, grid_cap ? grid_cap : 256 * 9)), dim3(64),
+  hipLaunchKernelGGL(k_gs_files_encode, dim3(grid_blocks(a.L.n_files, kWaveFiles, grid_cap ? grid_cap : 256 * 9)), dim3(64),
                      0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_gs_new_mark(hipStream_t s, GsTable t, const unsigned long long* sorted, uint32_t n, uint32_t* keep) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_gs_new_mark, dim3(blocks_for(n, 256 * kNewProbes, 2048)), dim3(256), 0, s, t, sorted, n, keep);
+  hipLaunchKernelGGL(k_gs_new_mark, dim3(grid_blocks(n, 256 * kNewProbes, 2048)), dim3(256), 0, s, t, sorted, n, keep);
   return hipGetLastError();
 }
 
 hipError_t launch_gs_new_compact(hipStream_t s, const unsigned long long* sorted, const uint32_t* keep,
                                  const uint32_t* pos, uint32_t n, unsigned long long* out) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_gs_new_compact, dim3(blocks_for(n, 256, 4096)), dim3(256), 0, s, sorted, keep, pos, n, out);
+  hipLaunchKernelGGL(k_gs_new_compact, dim3(grid_blocks(n, 256, 4096)), dim3(256), 0, s, sorted, keep, pos, n, out);
   return hipGetLastError();
 }
 

@@ -21,7 +21,7 @@
 
 #include "ce_common.h"
 #include "ce_dotset.h"
-#include "ce_orswot_write.h"
+#include "ce_opfile.h"
 
 namespace ce {
 
@@ -30,7 +30,6 @@ static constexpr uint32_t kRmFixedBytes = 26;  // ... and a7 "members" 91 behind
 static constexpr uint32_t kRmNoHandle = 0xffffffffu;
 static constexpr uint32_t kRmRunOps = 64;      // ops a wave encodes per trip, a lane each
 
-CE_HD constexpr uint32_t rm_map_hdr(uint32_t k) { return k <= 15 ? 1u : k <= 65535 ? 3u : 5u; }
 // the most clear text n_ops ops over e_ops entries (counted once an op) in F files can take
 CE_HD constexpr uint64_t rm_clear_bound(uint64_t n_ops, uint64_t e_ops, uint64_t F) {
   return F * (16 + 3) + n_ops * (kRmFixedBytes + 5 + 9) + e_ops * (18 + 9);
@@ -70,19 +69,12 @@ struct RmArgs {
   uint32_t* s_actor;            // [n_ent] actor id of sorted entry e
   unsigned long long* s_ctr;    // [n_ent] its counter
   // sizes and the encoder
-  uint32_t opf, n_ops, n_files;
+  uint32_t opf, n_ops;
   uint32_t* olen;               // [n_ops + 1] op byte lengths, olen[n_ops] = 0
   const uint32_t* ooff;         // [n_ops + 1] their exclusive sums
-  uint32_t* clen;               // [n_files + 1] clear lengths, clen[n_files] = 0
-  uint32_t* xlen;               // [n_files + 1] a sealed file's bytes past its clear text and kOwSealBase
-  const uint32_t* coff;         // [n_files + 1] exclusive sums of clen
-  const uint32_t* xoff;         //               and of xlen
-  uint8_t dv[16];               // the data version
+  OpFileLayout L;               // n_files = ceil(n_ops / opf); sized by launch_opfile_sizes
   uint32_t head[7];             // the 26 constant bytes of an op: [0, 17) up to the map header,
                                 // [17, 26) a7 "members" 91
-  uint8_t* clear;               // the clear texts back to back, 16-byte aligned
-  unsigned long long* offs;     // [n_files + 1] clear offsets for the seal
-  unsigned long long* file_offs;  // [n_files + 1] sealed offsets: coff + i * kOwSealBase + xoff
 };
 
 // first[handle of members[i]] = min(.., i), hnd[i]; then one scan of the pair table: cnt / ebytes
@@ -99,7 +91,6 @@ hipError_t launch_rm_scatter(hipStream_t s, const RmArgs& a);
 hipError_t launch_rm_gather(hipStream_t s, const RmArgs& a);
 hipError_t launch_rm_entries(hipStream_t s, const RmArgs& a);
 hipError_t launch_rm_op_sizes(hipStream_t s, const RmArgs& a);
-hipError_t launch_rm_file_sizes(hipStream_t s, const RmArgs& a);
 // the clear texts and the seal's two offset columns.  grid_cap: the most blocks (0: the default)
 hipError_t launch_rm_encode(hipStream_t s, const RmArgs& a, uint32_t grid_cap);
 

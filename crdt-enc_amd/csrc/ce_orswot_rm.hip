@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ce_dotset_device.h"
+#include "ce_opfile_device.h"
 #include "ce_orswot_rm.h"
 
 namespace ce {
@@ -17,47 +19,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr uint32_t kWin = 16384;  // the encoder's staging window: bytes of LDS a wave
-
-// an unsigned integer's encoded length: its smallest form (fixint, cc, cd, ce, cf)
-__device__ __forceinline__ uint32_t rm_width(unsigned long long v) {
-  return v <= 0x7f ? 1u : v <= 0xff ? 2u : v <= 0xffff ? 3u : v <= 0xffffffffull ? 5u : 9u;
-}
-__device__ __forceinline__ uint8_t rm_uint_byte(unsigned long long v, uint32_t wd, uint32_t k) {
-  if (k == 0) return wd == 1 ? (uint8_t)v : (uint8_t)(wd == 2 ? 0xcc : wd == 3 ? 0xcd : wd == 5 ? 0xce : 0xcf);
-  return (uint8_t)(v >> (8 * (wd - 1 - k)));
-}
-
-// member_find(t, m, false) of ce_dotset.hip: the same hash, window and overflow table
-constexpr uint32_t kMemberWindow = 32;
-__device__ __forceinline__ unsigned long long rm_mix64(unsigned long long x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
-__device__ unsigned long long rm_member_find(const DsTables& t, unsigned long long m) {
-  if (m == kDsEmpty) return (unsigned long long)t.smask + 1 + t.mmask + 1;  // the reserved slot
-  const unsigned long long x = rm_mix64(m);
-  uint32_t h = (uint32_t)x & t.smask;
-  for (uint32_t probe = 0; probe < kMemberWindow; probe++) {
-    const unsigned long long k = t.mkey[h];
-    if (k == m) return h;
-    if (k == kDsEmpty) return kDsEmpty;
-    h = (h + 1) & t.smask;
-  }
-  const unsigned long long base = (unsigned long long)t.smask + 1;
-  const unsigned long long* ov = t.mkey + base;
-  h = (uint32_t)(x >> 32) & t.mmask;
-  for (uint32_t probe = 0; probe <= t.mmask; probe++) {
-    const unsigned long long k = ov[h];
-    if (k == m) return base + h;
-    if (k == kDsEmpty) return kDsEmpty;
-    h = (h + 1) & t.mmask;
-  }
-  return kDsEmpty;
-}
 
 __device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
 #pragma unroll
@@ -72,7 +33,7 @@ __device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
 // word a member slot); members 0 and ~0 take the lookup's own paths
 __global__ void __launch_bounds__(kBlock) k_rm_mark(RmArgs a) {
   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < a.n; i += gridDim.x * kBlock) {
-    const unsigned long long h = rm_member_find(a.t, a.members[i]);
+    const unsigned long long h = member_find(a.t, a.members[i], false);
     a.hnd[i] = h == kDsEmpty ? kRmNoHandle : (uint32_t)h;
     if (h != kDsEmpty) atomicMin(a.first + h, i);
   }
@@ -96,7 +57,7 @@ __global__ void __launch_bounds__(kBlock) k_rm_count(RmArgs a) {
     const uint32_t r = a.first[key >> kDsActorBits];
     if (r >= a.n) continue;
     atomicAdd(a.cnt + r, 1u);
-    atomicAdd(a.ebytes + r, 18u + rm_width(v));
+    atomicAdd(a.ebytes + r, 18u + uint_width(v));
   }
 }
 
@@ -168,7 +129,7 @@ __global__ void __launch_bounds__(kBlock) k_rm_entries(RmArgs a) {
 
 // ops of file f (0 past the last)
 __device__ __forceinline__ uint32_t file_ops(const RmArgs& a, uint32_t f) {
-  if (f >= a.n_files) return 0;
+  if (f >= a.L.n_files) return 0;
   const uint32_t left = a.n_ops - f * a.opf;
   return left < a.opf ? left : a.opf;
 }
@@ -178,19 +139,7 @@ __global__ void __launch_bounds__(kBlock) k_rm_op_sizes(RmArgs a) {
   if (blockIdx.x == 0 && threadIdx.x == 0) a.olen[a.n_ops] = 0;
   for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < a.n_ops; j += gridDim.x * kBlock) {
     const uint32_t p = a.op_pos[j], r = a.rep[p];
-    a.olen[j] = kRmFixedBytes + rm_map_hdr(a.cnt[r]) + a.ebytes[r] + rm_width(a.members[p]);
-  }
-}
-
-// The file size pass, a lane per file: the data version, the Vec's header and its ops' bytes; the
-// envelope's two bin headers at whatever form the length takes.
-__global__ void __launch_bounds__(kBlock) k_rm_file_sizes(RmArgs a) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) a.clen[a.n_files] = a.xlen[a.n_files] = 0;
-  for (uint32_t f = blockIdx.x * kBlock + threadIdx.x; f < a.n_files; f += gridDim.x * kBlock) {
-    const uint32_t nops = file_ops(a, f), j0 = f * a.opf;
-    const uint32_t len = 16 + ow_arr_hdr(nops) + (a.ooff[j0 + nops] - a.ooff[j0]);
-    a.clen[f] = len;
-    a.xlen[f] = (uint32_t)(16 + sealed_len(len) - len - kOwSealBase);
+    a.olen[j] = kRmFixedBytes + rm_map_hdr(a.cnt[r]) + a.ebytes[r] + uint_width(a.members[p]);
   }
 }
 
@@ -208,15 +157,13 @@ struct RmOut {
 // The encoder: one wave a block, kRmRunOps consecutive ops a trip, a lane an op.  The run's bytes
 // are one range [b0, b1) of the clear blob -- a file's data version and Vec header belong to the
 // lane of the file's first op -- staged in LDS a window of kWin bytes at a time, at the same
-// offset mod 16 as in the blob, so a window leaves as aligned 16-byte stores; only the run's first
-// and last partial chunk, shared with the neighbouring runs, leave byte by byte.  A lane walks its
-// op once per window the op touches, stepping over the entries before the window by their widths.
+// offset mod 16 as in the blob (opfile_flush).  A lane walks its op once per window the op
+// touches, stepping over the entries before the window by their widths.
 __global__ void __launch_bounds__(64) k_rm_encode(RmArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[kWin];
   const uint8_t* head = reinterpret_cast<const uint8_t*>(a.head);
   const uint32_t lane = threadIdx.x;
   const uint32_t runs = (a.n_ops + kRmRunOps - 1) / kRmRunOps;
-  const uint32_t F = a.n_files;
   for (uint32_t run = blockIdx.x; run < runs; run += gridDim.x) {
     const uint32_t j0 = run * kRmRunOps;
     const uint32_t cnt_run = a.n_ops - j0 < kRmRunOps ? a.n_ops - j0 : kRmRunOps;
@@ -228,25 +175,18 @@ __global__ void __launch_bounds__(64) k_rm_encode(RmArgs a) {
     if (mine) {
       const uint32_t f = j / a.opf, kf = j - f * a.opf;
       nops_f = file_ops(a, f);
-      const uint32_t cf = a.coff[f];
-      at = cf + 16 + ow_arr_hdr(nops_f) + (a.ooff[j] - a.ooff[f * a.opf]);
+      const uint32_t cf = a.L.coff[f];
+      at = cf + 16 + arr_hdr_len(nops_f) + (a.ooff[j] - a.ooff[f * a.opf]);
       wend = at + (a.ooff[j + 1] - a.ooff[j]);
       file_head = kf == 0;
       wstart = file_head ? cf : at;
-      if (file_head) {
-        a.offs[f] = cf;
-        a.file_offs[f] = (unsigned long long)cf + (unsigned long long)f * kOwSealBase + a.xoff[f];
-        if (f == F - 1) {
-          a.offs[F] = a.coff[F];
-          a.file_offs[F] = (unsigned long long)a.coff[F] + (unsigned long long)F * kOwSealBase + a.xoff[F];
-        }
-      }
+      if (file_head) opfile_publish_offsets(a.L, f);
       const uint32_t p = a.op_pos[j], r = a.rep[p];
       k = a.cnt[r];
       e0 = a.ebeg[r];
       if (e0 > a.n_ent || k > a.n_ent - e0) k = 0;  // (never: the scans agree)
       m = a.members[p];
-      wm = rm_width(m);
+      wm = uint_width(m);
     }
     const uint32_t b0 = (uint32_t)__shfl((int)wstart, 0);
     const uint32_t b1 = (uint32_t)__shfl((int)wend, (int)cnt_run - 1);
@@ -256,14 +196,9 @@ __global__ void __launch_bounds__(64) k_rm_encode(RmArgs a) {
         RmOut o{stage, w0, lo, hi - lo, wstart};
         if (file_head) {
 #pragma unroll
-          for (uint32_t b = 0; b < 16; b++) o.put(a.dv[b]);
-          if (nops_f <= 15) {
-            o.put((uint8_t)(0x90 | nops_f));
-          } else {
-            o.put(0xdc);
-            o.put((uint8_t)(nops_f >> 8));
-            o.put((uint8_t)nops_f);
-          }
+          for (uint32_t b = 0; b < 16; b++) o.put(a.L.dv[b]);
+          const uint32_t hv = arr_hdr_len(nops_f);
+          for (uint32_t b = 0; b < hv; b++) o.put(arr_hdr_byte(nops_f, hv, b));
         }
 #pragma unroll
         for (uint32_t b = 0; b < kRmHeadBytes; b++) o.put(head[b]);
@@ -283,7 +218,7 @@ __global__ void __launch_bounds__(64) k_rm_encode(RmArgs a) {
         for (uint32_t e = e0; e < e0 + k; e++) {
           if (o.pos >= hi) break;
           const unsigned long long c = a.s_ctr[e];
-          const uint32_t wd = rm_width(c);
+          const uint32_t wd = uint_width(c);
           if (o.pos + 18 + wd <= lo) {  // wholly before the window
             o.pos += 18 + wd;
             continue;
@@ -295,24 +230,15 @@ __global__ void __launch_bounds__(64) k_rm_encode(RmArgs a) {
           o.put(0x10);
 #pragma unroll
           for (uint32_t b = 0; b < 16; b++) o.put((uint8_t)(uw[b >> 2] >> (8 * (b & 3))));
-          for (uint32_t b = 0; b < wd; b++) o.put(rm_uint_byte(c, wd, b));
+          for (uint32_t b = 0; b < wd; b++) o.put(uint_byte(c, wd, b));
         }
         o.pos = wend - wm - (kRmFixedBytes - kRmHeadBytes);  // a7 "members" 91 <member>
 #pragma unroll
         for (uint32_t b = kRmHeadBytes; b < kRmFixedBytes; b++) o.put(head[b]);
-        for (uint32_t b = 0; b < wm; b++) o.put(rm_uint_byte(m, wm, b));
+        for (uint32_t b = 0; b < wm; b++) o.put(uint_byte(m, wm, b));
       }
       __syncthreads();
-      uint8_t* g16 = a.clear + w0;  // 16-byte aligned: stage[b] belongs at g16[b]
-      for (uint32_t c = lane * 16; c < kWin && w0 + c < hi; c += 64 * 16) {
-        const uint32_t g = w0 + c;
-        if (g >= lo && g + 16 <= hi) {
-          *reinterpret_cast<uint4*>(g16 + c) = *reinterpret_cast<const uint4*>(stage + c);
-        } else {
-          const uint32_t c0 = g < lo ? lo - w0 : c, c1 = g + 16 < hi ? c + 16 : hi - w0;
-          for (uint32_t b = c0; b < c1; b++) g16[b] = stage[b];
-        }
-      }
+      opfile_flush(stage, a.L.clear, w0, lo, hi, lane);
       __syncthreads();  // the stage is rewritten by the next window
     }
   }
@@ -338,77 +264,66 @@ __global__ void __launch_bounds__(kBlock) k_rm_cols(RmCols a) {
   }
 }
 
-uint32_t blocks_for(uint64_t work, uint32_t per_block, uint32_t cap) {
-  const uint64_t b = (work + per_block - 1) / per_block;
-  return b < 1 ? 1u : (b > cap ? cap : (uint32_t)b);
-}
-
 }  // namespace
 
 hipError_t launch_rm_mark(hipStream_t s, const RmArgs& a) {
   if (a.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rm_mark, dim3(blocks_for(a.n, kBlock, 4096)), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(k_rm_mark, dim3(grid_blocks(a.n, kBlock, 4096)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_rm_unmark(hipStream_t s, const RmArgs& a) {
   if (a.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rm_unmark, dim3(blocks_for(a.n, kBlock, 4096)), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(k_rm_unmark, dim3(grid_blocks(a.n, kBlock, 4096)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_rm_count(hipStream_t s, const RmArgs& a) {
   if (a.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rm_count, dim3(blocks_for((uint64_t)a.t.pmask + 1, kBlock, 2048)), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(k_rm_count, dim3(grid_blocks((uint64_t)a.t.pmask + 1, kBlock, 2048)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_rm_keep(hipStream_t s, const RmArgs& a) {
   if (a.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rm_keep, dim3(blocks_for(a.n, kBlock, 1024)), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(k_rm_keep, dim3(grid_blocks(a.n, kBlock, 1024)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_rm_scatter(hipStream_t s, const RmArgs& a) {
   if (a.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rm_scatter, dim3(blocks_for(a.n, kBlock, 4096)), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(k_rm_scatter, dim3(grid_blocks(a.n, kBlock, 4096)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_rm_gather(hipStream_t s, const RmArgs& a) {
   if (a.n_ent == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rm_gather, dim3(blocks_for((uint64_t)a.t.pmask + 1, kBlock, 2048)), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(k_rm_gather, dim3(grid_blocks((uint64_t)a.t.pmask + 1, kBlock, 2048)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_rm_entries(hipStream_t s, const RmArgs& a) {
   if (a.n_ent == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rm_entries, dim3(blocks_for(a.n_ent, kBlock, 4096)), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(k_rm_entries, dim3(grid_blocks(a.n_ent, kBlock, 4096)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_rm_op_sizes(hipStream_t s, const RmArgs& a) {
   if (a.n_ops == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rm_op_sizes, dim3(blocks_for(a.n_ops, kBlock, 4096)), dim3(kBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_rm_file_sizes(hipStream_t s, const RmArgs& a) {
-  if (a.n_files == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rm_file_sizes, dim3(blocks_for(a.n_files, kBlock, 4096)), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(k_rm_op_sizes, dim3(grid_blocks(a.n_ops, kBlock, 4096)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_rm_encode(hipStream_t s, const RmArgs& a, uint32_t grid_cap) {
   if (a.n_ops == 0) return hipSuccess;
   // one wave and 16 KiB of LDS a block: nine blocks resident a CU (160 KiB), the LDS the limit
-  hipLaunchKernelGGL(k_rm_encode, dim3(blocks_for(a.n_ops, kRmRunOps, grid_cap ? grid_cap : 256 * 9)), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(k_rm_encode, dim3(grid_blocks(a.n_ops, kRmRunOps, grid_cap ? grid_cap : 256 * 9)), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_rm_cols(hipStream_t s, const RmCols& a) {
   if (a.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rm_cols, dim3(blocks_for(a.n > a.n_ent ? a.n : a.n_ent, kBlock, 4096)), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(k_rm_cols, dim3(grid_blocks(a.n > a.n_ent ? a.n : a.n_ent, kBlock, 4096)), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

@@ -13,7 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "ce_common.h"
+#include "ce_opfile.h"
 
 namespace ce {
 
@@ -23,16 +23,12 @@ static constexpr uint32_t kOwFixedBytes = 51;  // ... and the a7 "members" behin
 // ops of fewer members than this are sized and encoded a lane per op, longer ones a 16-lane
 // group per op (the members' array header changes form at the same count)
 static constexpr uint32_t kOwGroupOps = 16;
-// the least a sealed file adds to its clear text: the outer version and an envelope whose two bin
-// headers are bin8
-static constexpr uint64_t kOwSealBase = 16 + sealed_len(0);
 
-CE_HD constexpr uint32_t ow_arr_hdr(uint32_t cnt) { return cnt <= 15 ? 1u : 3u; }  // (cnt < 65536)
 // an op's worst case: a 9-byte counter and 9-byte members
-CE_HD constexpr uint64_t ow_op_bound(uint64_t cnt) { return kOwFixedBytes + 9 + ow_arr_hdr((uint32_t)cnt) + 9 * cnt; }
+CE_HD constexpr uint64_t ow_op_bound(uint64_t cnt) { return kOwFixedBytes + 9 + arr_hdr_len((uint32_t)cnt) + 9 * cnt; }
 // a file's worst case; the one-page rule is ow_file_bound(ops_per_file, per_op) <= kOwPage
 CE_HD constexpr uint64_t ow_file_bound(uint64_t ops, uint64_t per_op) {
-  return 16 + ow_arr_hdr((uint32_t)(ops > 65535 ? 65535 : ops)) + ops * ow_op_bound(per_op);
+  return 16 + arr_hdr_len((uint32_t)(ops > 65535 ? 65535 : ops)) + ops * ow_op_bound(per_op);
 }
 
 struct OwArgs {
@@ -40,26 +36,17 @@ struct OwArgs {
   unsigned long long n;
   unsigned long long c0;       // the local actor's counter before the call: op j carries c0 + 1 + j
   uint32_t per_op, opf;        // members an op, ops a file
-  uint32_t n_ops, n_files;     // ceil(n / per_op) > 0, ceil(n_ops / opf)
+  uint32_t n_ops;              // ceil(n / per_op) > 0
   uint32_t* olen;              // [n_ops + 1] op byte lengths, olen[n_ops] = 0 (the op size pass)
   const uint32_t* ooff;        // [n_ops + 1] their exclusive sums
-  uint32_t* clen;              // [n_files + 1] clear lengths, clen[n_files] = 0 (the file size pass)
-  uint32_t* xlen;              // [n_files + 1] a sealed file's bytes past its clear text and kOwSealBase
-  const uint32_t* coff;        // [n_files + 1] exclusive sums of clen (the encoder)
-  const uint32_t* xoff;        //               and of xlen
-  uint8_t dv[16];              // the data version
+  OpFileLayout L;              // n_files = ceil(n_ops / opf); sized by launch_opfile_sizes
   // the per-call constant of every op: bytes [0, 43) the op up to its counter (the local actor
   // inside), bytes [43, 51) a7 "members", one pad byte
   uint32_t head[13];
-  uint8_t* clear;              // the clear texts back to back, 16-byte aligned
-  unsigned long long* offs;    // [n_files + 1] clear offsets for the seal
-  unsigned long long* file_offs;  // [n_files + 1] sealed offsets: coff + i * kOwSealBase + xoff
 };
 
 // olen[j] for every op, olen[n_ops] = 0
 hipError_t launch_ow_op_sizes(hipStream_t s, const OwArgs& a);
-// clen / xlen for every file from ooff, clen[n_files] = xlen[n_files] = 0
-hipError_t launch_ow_file_sizes(hipStream_t s, const OwArgs& a);
 // the clear texts, and the seal's two offset columns.  grid_cap: the most blocks (0: the default)
 hipError_t launch_ow_encode(hipStream_t s, const OwArgs& a, uint32_t grid_cap);
 

@@ -9,44 +9,25 @@
 // The work unit follows the op's length, in the size pass and in the encoder alike: ops of fewer
 // than kOwGroupOps members (a fixarray of members; C3's one-member ops among them) take a lane
 // each, which needs no cross-lane step at all -- the op's start comes from the scanned lengths;
-// longer ops (add_all's shape) take a 16-lane group each, the members 16 to a round with a prefix
-// of their widths, as the GSet writer lays out a file.
+// longer ops (add_all's shape) take a 16-lane group each (group_width_sum, group_put_members), as
+// the GSet writer lays out a file.  The file size pass is the shared one (ce_opfile.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ce_opfile_device.h"
 #include "ce_orswot_write.h"
 
 namespace ce {
 namespace {
 
-constexpr uint32_t kGroup = 16;     // lanes per file, the readers' geometry
+constexpr uint32_t kGroup = kOpFileGroup;
 constexpr uint32_t kWaveFiles = 4;  // files per wave and trip
 // the wave's files lie back to back in the clear blob; they are staged at the same offset mod 16
 constexpr uint32_t kStageBytes = kWaveFiles * kOwPage + 16;
 
-// an unsigned integer's encoded length: its smallest form (fixint, cc, cd, ce, cf)
-__device__ __forceinline__ uint32_t ow_width(unsigned long long v) {
-  return v <= 0x7f ? 1u : v <= 0xff ? 2u : v <= 0xffff ? 3u : v <= 0xffffffffull ? 5u : 9u;
-}
-// byte k of that form (wd = ow_width(v))
-__device__ __forceinline__ uint8_t ow_uint_byte(unsigned long long v, uint32_t wd, uint32_t k) {
-  if (k == 0) return wd == 1 ? (uint8_t)v : (uint8_t)(wd == 2 ? 0xcc : wd == 3 ? 0xcd : wd == 5 ? 0xce : 0xcf);
-  return (uint8_t)(v >> (8 * (wd - 1 - k)));
-}
-// byte k of an array header of hc = ow_arr_hdr(cnt) bytes
-__device__ __forceinline__ uint8_t ow_hdr_byte(uint32_t cnt, uint32_t hc, uint32_t k) {
-  if (hc == 1) return (uint8_t)(0x90 | cnt);
-  return k == 0 ? (uint8_t)0xdc : k == 1 ? (uint8_t)(cnt >> 8) : (uint8_t)cnt;
-}
-__device__ __forceinline__ uint32_t ow_put_uint(uint8_t* p, unsigned long long v) {
-  const uint32_t wd = ow_width(v);
-  for (uint32_t k = 0; k < wd; k++) p[k] = ow_uint_byte(v, wd, k);
-  return wd;
-}
-
 // ops of file f, members of op j (0 past the last)
 __device__ __forceinline__ uint32_t file_ops(const OwArgs& a, uint32_t f) {
-  if (f >= a.n_files) return 0;
+  if (f >= a.L.n_files) return 0;
   const unsigned long long left = a.n_ops - (unsigned long long)f * a.opf;
   return left < a.opf ? (uint32_t)left : a.opf;
 }
@@ -57,8 +38,7 @@ __device__ __forceinline__ uint32_t op_count(const OwArgs& a, unsigned long long
 }
 
 // The op size pass.  Short ops: a lane per op.  Long ops: a 16-lane group per op sums its members'
-// widths (lane sub: members sub + 16 k); every lane of a block runs the same trips, so the
-// shuffles see whole groups.
+// widths; every lane of a block runs the same trips, so the shuffles see whole groups.
 __global__ __launch_bounds__(256) void k_ow_op_sizes(OwArgs a) {
   if (blockIdx.x == 0 && threadIdx.x == 0) a.olen[a.n_ops] = 0;
   if (a.per_op < kOwGroupOps) {
@@ -67,8 +47,8 @@ __global__ __launch_bounds__(256) void k_ow_op_sizes(OwArgs a) {
       const uint32_t cnt = op_count(a, j);
       const unsigned long long* m = a.members + j * a.per_op;
       uint32_t sum = 0;
-      for (uint32_t e = 0; e < cnt; e++) sum += ow_width(m[e]);
-      a.olen[j] = kOwFixedBytes + ow_width(a.c0 + 1 + j) + ow_arr_hdr(cnt) + sum;
+      for (uint32_t e = 0; e < cnt; e++) sum += uint_width(m[e]);
+      a.olen[j] = kOwFixedBytes + uint_width(a.c0 + 1 + j) + arr_hdr_len(cnt) + sum;
     }
     return;
   }
@@ -78,24 +58,8 @@ __global__ __launch_bounds__(256) void k_ow_op_sizes(OwArgs a) {
   for (unsigned long long base = (unsigned long long)blockIdx.x * per_block; base < a.n_ops; base += stride) {
     const unsigned long long j = base + threadIdx.x / kGroup;
     const uint32_t cnt = op_count(a, j);
-    const unsigned long long* m = a.members + j * a.per_op;
-    uint32_t sum = 0;
-    for (uint32_t e = sub; e < cnt; e += kGroup) sum += ow_width(m[e]);
-#pragma unroll
-    for (int d = 1; d < (int)kGroup; d <<= 1) sum += (uint32_t)__shfl_xor((int)sum, d, kGroup);
-    if (j < a.n_ops && sub == 0) a.olen[j] = kOwFixedBytes + ow_width(a.c0 + 1 + j) + ow_arr_hdr(cnt) + sum;
-  }
-}
-
-// The file size pass, a lane per file: the data version, the Vec's header and its ops' bytes.
-__global__ __launch_bounds__(256) void k_ow_file_sizes(OwArgs a) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) a.clen[a.n_files] = a.xlen[a.n_files] = 0;
-  for (uint32_t f = blockIdx.x * 256 + threadIdx.x; f < a.n_files; f += gridDim.x * 256) {
-    const uint32_t nops = file_ops(a, f);
-    const unsigned long long j0 = (unsigned long long)f * a.opf;
-    const uint32_t len = 16 + ow_arr_hdr(nops) + (a.ooff[j0 + nops] - a.ooff[j0]);
-    a.clen[f] = len;
-    a.xlen[f] = (uint32_t)(16 + sealed_len(len) - len - kOwSealBase);
+    const uint32_t sum = group_width_sum(a.members + j * a.per_op, cnt, sub);
+    if (j < a.n_ops && sub == 0) a.olen[j] = kOwFixedBytes + uint_width(a.c0 + 1 + j) + arr_hdr_len(cnt) + sum;
   }
 }
 
@@ -105,29 +69,27 @@ __device__ __forceinline__ void write_op_lane(uint8_t* p, const OwArgs& a, const
 #pragma unroll
   for (uint32_t k = 0; k < kOwHeadBytes; k++) p[k] = head[k];
   p += kOwHeadBytes;
-  p += ow_put_uint(p, a.c0 + 1 + j);
+  p += put_uint(p, a.c0 + 1 + j);
 #pragma unroll
   for (uint32_t k = kOwHeadBytes; k < kOwFixedBytes; k++) p[k - kOwHeadBytes] = head[k];
   p += kOwFixedBytes - kOwHeadBytes;
   const uint32_t cnt = op_count(a, j);  // (< kOwGroupOps: a fixarray)
   *p++ = (uint8_t)(0x90 | cnt);
   const unsigned long long* m = a.members + j * a.per_op;
-  for (uint32_t e = 0; e < cnt; e++) p += ow_put_uint(p, m[e]);
+  for (uint32_t e = 0; e < cnt; e++) p += put_uint(p, m[e]);
 }
 
 // The encoder: one wave per block, kWaveFiles files per trip, group q staging file f0 + q in LDS.
 // Short ops: lane sub writes ops sub, sub + 16, ... of its file, each at the start the scanned
 // lengths give it.  Long ops: the group writes its file's ops one after another -- the up to 63
-// bytes before the members spread over the lanes, then the members 16 to a round, a 16-lane prefix
-// of the widths carrying the running byte offset; every lane of the wave runs opf x rounds trips.
-// The wave's files are one byte range [b0, b1) of the clear blob, staged at b0's offset mod 16,
-// so the range leaves as aligned 16-byte stores; only its first and last partial chunk, shared
-// with the neighbouring waves' ranges, leave byte by byte.
+// bytes before the members spread over the lanes, then the members (group_put_members); every
+// lane of the wave runs opf x rounds trips.  The wave's files are one byte range [b0, b1) of the
+// clear blob, staged at b0's offset mod 16 (opfile_flush).
 __global__ __launch_bounds__(64) void k_ow_encode(OwArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[kStageBytes];
   const uint8_t* head = reinterpret_cast<const uint8_t*>(a.head);
   const uint32_t lane = threadIdx.x, q = lane / kGroup, sub = lane & (kGroup - 1);
-  const uint32_t F = a.n_files;
+  const uint32_t F = a.L.n_files;
   const uint32_t trips = (F + kWaveFiles - 1) / kWaveFiles;
   const bool lane_ops = a.per_op < kOwGroupOps;
   const uint32_t op_rounds = (a.opf + kGroup - 1) / kGroup;
@@ -135,28 +97,20 @@ __global__ __launch_bounds__(64) void k_ow_encode(OwArgs a) {
   for (uint32_t w = blockIdx.x; w < trips; w += gridDim.x) {
     const uint32_t f0 = w * kWaveFiles;
     const uint32_t f1 = f0 + kWaveFiles < F ? f0 + kWaveFiles : F;
-    const uint32_t b0 = a.coff[f0], b1 = a.coff[f1];
-    const uint32_t shift = b0 & 15;
+    const uint32_t b0 = a.L.coff[f0], b1 = a.L.coff[f1];  // b1 - b0 <= kWaveFiles * kOwPage
     const uint32_t f = f0 + q;
-    const bool mine = f < F;
     const uint32_t nops = file_ops(a, f);
     const unsigned long long j0 = (unsigned long long)f * a.opf;
     uint32_t body = 0, ob0 = 0;  // the first op's byte in the stage, and in the scanned lengths
-    if (mine) {
-      const uint32_t cf = a.coff[f];
-      const uint32_t at = shift + (cf - b0);
+    if (f < F) {
+      const uint32_t at = (b0 & 15) + (a.L.coff[f] - b0);
       if (sub == 0) {
-        a.offs[f] = cf;
-        a.file_offs[f] = (unsigned long long)cf + (unsigned long long)f * kOwSealBase + a.xoff[f];
-        if (f == F - 1) {
-          a.offs[F] = a.coff[F];
-          a.file_offs[F] = (unsigned long long)a.coff[F] + (unsigned long long)F * kOwSealBase + a.xoff[F];
-        }
-        const uint32_t hv = ow_arr_hdr(nops);
-        for (uint32_t k = 0; k < hv; k++) stage[at + 16 + k] = ow_hdr_byte(nops, hv, k);
+        opfile_publish_offsets(a.L, f);
+        const uint32_t hv = arr_hdr_len(nops);
+        for (uint32_t k = 0; k < hv; k++) stage[at + 16 + k] = arr_hdr_byte(nops, hv, k);
       }
-      stage[at + sub] = a.dv[sub];
-      body = at + 16 + ow_arr_hdr(nops);
+      stage[at + sub] = a.L.dv[sub];
+      body = at + 16 + arr_hdr_len(nops);
       ob0 = a.ooff[j0];
     }
     if (lane_ops) {
@@ -173,50 +127,23 @@ __global__ __launch_bounds__(64) void k_ow_encode(OwArgs a) {
         if (has_op) {
           const uint32_t at = body + (a.ooff[j] - ob0);
           const unsigned long long ctr = a.c0 + 1 + j;
-          const uint32_t wc = ow_width(ctr), hc = ow_arr_hdr(cnt);
+          const uint32_t wc = uint_width(ctr), hc = arr_hdr_len(cnt);
           const uint32_t pre = kOwFixedBytes + wc + hc;  // <= 63
           for (uint32_t b = sub; b < pre; b += kGroup) {
             uint8_t v;
             if (b < kOwHeadBytes) v = head[b];
-            else if (b < kOwHeadBytes + wc) v = ow_uint_byte(ctr, wc, b - kOwHeadBytes);
+            else if (b < kOwHeadBytes + wc) v = uint_byte(ctr, wc, b - kOwHeadBytes);
             else if (b < kOwFixedBytes + wc) v = head[b - wc];
-            else v = ow_hdr_byte(cnt, hc, b - kOwFixedBytes - wc);
+            else v = arr_hdr_byte(cnt, hc, b - kOwFixedBytes - wc);
             stage[at + b] = v;
           }
           run = at + pre;
         }
-        const unsigned long long* m = a.members + j * a.per_op;
-        for (uint32_t r = 0; r < mem_rounds; r++) {
-          const uint32_t e = r * kGroup + sub;
-          const bool has = e < cnt;
-          const unsigned long long x = has ? m[e] : 0ull;
-          const uint32_t wd = has ? ow_width(x) : 0u;
-          uint32_t incl = wd;
-#pragma unroll
-          for (int d = 1; d < (int)kGroup; d <<= 1) {
-            const uint32_t t = (uint32_t)__shfl_up((int)incl, d, kGroup);
-            if (sub >= (uint32_t)d) incl += t;
-          }
-          const uint32_t total = (uint32_t)__shfl((int)incl, kGroup - 1, kGroup);
-          if (has) {
-            uint8_t* p = stage + run + incl - wd;
-            for (uint32_t b = 0; b < wd; b++) p[b] = ow_uint_byte(x, wd, b);
-          }
-          run += total;
-        }
+        group_put_members(stage, run, a.members + j * a.per_op, cnt, mem_rounds, sub);
       }
     }
     __syncthreads();
-    const uint32_t end = shift + (b1 - b0);  // <= 15 + kWaveFiles * kOwPage < kStageBytes
-    uint8_t* g16 = a.clear + (b0 - shift);    // 16-byte aligned: stage[b] belongs at g16[b]
-    for (uint32_t lo = lane * 16; lo < end; lo += 64 * 16) {
-      if (lo >= shift && lo + 16 <= end) {
-        *reinterpret_cast<uint4*>(g16 + lo) = *reinterpret_cast<const uint4*>(stage + lo);
-      } else {
-        const uint32_t c0 = lo < shift ? shift : lo, c1 = lo + 16 < end ? lo + 16 : end;
-        for (uint32_t b = c0; b < c1; b++) g16[b] = stage[b];
-      }
-    }
+    opfile_flush(stage, a.L.clear, b0 & ~15u, b0, b1, lane);
     __syncthreads();  // the stage is rewritten by the next trip
   }
 }
@@ -240,38 +167,27 @@ __global__ __launch_bounds__(256) void k_ow_cols(OwCols a) {
   }
 }
 
-uint32_t blocks_for(uint64_t work, uint32_t per_block, uint32_t cap) {
-  const uint64_t b = (work + per_block - 1) / per_block;
-  return b < 1 ? 1u : (b > cap ? cap : (uint32_t)b);
-}
-
 }  // namespace
 
 hipError_t launch_ow_op_sizes(hipStream_t s, const OwArgs& a) {
   if (a.n_ops == 0) return hipSuccess;
   const uint32_t per_block = a.per_op < kOwGroupOps ? 256u : 256u / kGroup;
-  hipLaunchKernelGGL(k_ow_op_sizes, dim3(blocks_for(a.n_ops, per_block, 4096)), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_ow_file_sizes(hipStream_t s, const OwArgs& a) {
-  if (a.n_files == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_ow_file_sizes, dim3(blocks_for(a.n_files, 256, 4096)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_ow_op_sizes, dim3(grid_blocks(a.n_ops, per_block, 4096)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_ow_encode(hipStream_t s, const OwArgs& a, uint32_t grid_cap) {
-  if (a.n_files == 0) return hipSuccess;
+  if (a.L.n_files == 0) return hipSuccess;
   // one wave and 16,400 bytes of LDS a block: nine blocks resident a CU (160 KiB), the LDS the
   // limit -- nine waves of staging and byte stores a CU, no other resource near its bound
-  hipLaunchKernelGGL(k_ow_encode, dim3(blocks_for(a.n_files, kWaveFiles, grid_cap ? grid_cap : 256 * 9)), dim3(64), 0,
+  hipLaunchKernelGGL(k_ow_encode, dim3(grid_blocks(a.L.n_files, kWaveFiles, grid_cap ? grid_cap : 256 * 9)), dim3(64), 0,
                      s, a);
   return hipGetLastError();
 }
 
 hipError_t launch_ow_cols(hipStream_t s, const OwCols& a) {
   if (a.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_ow_cols, dim3(blocks_for(a.n, 256, 4096)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_ow_cols, dim3(grid_blocks(a.n, 256, 4096)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
